@@ -2,7 +2,8 @@
 """Flagship benchmark: jobs dispatched/sec (whole node) + p50 dispatch->result
 latency — the BASELINE.json metric on synthetic echo jobs.
 
-Two timed windows, both reported in the ONE output line:
+A plain run times ONE window and reports it in the ONE output line; `--full`
+adds the second window to the same line:
 
 1. END-TO-END INGEST (the headline `value`): each step encodes a FRESH random
    job batch on the host (vectorized JobEncoder semantics, new content every
@@ -12,8 +13,8 @@ Two timed windows, both reported in the ONE output line:
    device echo workers -> SUCCEEDED), and reads the per-job results
    (checksums + decisions) back to the host. Encode, H2D, tick and D2H are
    all inside the timed region.
-2. IN-HBM TICK (`config.in_hbm_tick_jobs_per_s`): the steady-state dispatch
-   tick over batches resident in HBM (a ring of pre-staged distinct batches,
+2. IN-HBM TICK (`--full` only, `config.in_hbm_tick_jobs_per_s`): the
+   steady-state dispatch tick over batches resident in HBM (a ring of pre-staged distinct batches,
    hipGraph-captured) — the rate of the dispatch engine itself once jobs are
    in device memory.
 
@@ -21,7 +22,12 @@ Counting: `value` counts DISPATCHED+COMPLETED jobs only; DENIED jobs are
 reported separately in config.denied_jobs (they are decided, not dispatched).
 
 Usage (the driver contract):
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+                  [--dump-outputs DIR]
+`--dump-outputs DIR` writes what the last timed ingest step returned to its
+caller (per-job result checksums + policy decisions, and the window's job
+totals) as DIR/<name>.npy; inputs are seeded per (seed, step), so two builds
+run with the same arguments can be compared output for output.
 For N > 1 the driver launches via torch.distributed.run with one rank per
 GPU; ranks read RANK/LOCAL_RANK/WORLD_SIZE from the env.
 """
@@ -150,9 +156,16 @@ def main() -> int:
     ap.add_argument("--workflow", action="store_true",
                     help="config #3 mode: device workflow engine waves "
                          "(1->fanout fan-out + approval gate per run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the in-HBM steady-state tick window "
+                         "(second pipeline; config.in_hbm_tick_*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--runs", type=int, default=2048, help="workflow runs per rank per wave")
     ap.add_argument("--fanout", type=int, default=256, help="for_each children per run")
     args = ap.parse_args()
+    if args.workflow and args.dump_outputs:
+        ap.error("--dump-outputs covers the flagship ingest window, not --workflow")
 
     import torch
 
@@ -186,16 +199,19 @@ def main() -> int:
 
     if args.workflow:
         return run_workflow_bench(args, device, world_size, rank, backend, use_gpu)
-    pipe = DevicePipeline(
-        device=device,
-        batch_size=args.batch,
-        n_local_workers=args.workers,
-        n_rules=args.rules,
-        payload_words=max(1, args.payload_bytes // 4),
-        world_size=world_size,
-        rank=rank,
-        backend=backend,
-    )
+    # in-HBM window pipeline (--full only)
+    pipe = None
+    if args.full:
+        pipe = DevicePipeline(
+            device=device,
+            batch_size=args.batch,
+            n_local_workers=args.workers,
+            n_rules=args.rules,
+            payload_words=max(1, args.payload_bytes // 4),
+            world_size=world_size,
+            rank=rank,
+            backend=backend,
+        )
     # e2e window pipeline: the captured graph reads the staging tensors the
     # per-step H2D copies write — MFMA K1 included, via the device-side job
     # pack kernel (falls back to the bitset K1 outside the MFMA envelope)
@@ -218,9 +234,10 @@ def main() -> int:
         if use_gpu:
             torch.cuda.synchronize(device)
 
-    # warmup both windows (graph capture, allocator steady state, RCCL init)
-    for _ in range(args.warmup):
-        pipe.tick()
+    # warmup the timed windows (graph capture, allocator steady state, RCCL init)
+    if pipe is not None:
+        for _ in range(args.warmup):
+            pipe.tick()
     pipe_e2e.e2e_run(max(2, args.warmup))
     barrier()
 
@@ -244,35 +261,47 @@ def main() -> int:
     barrier()
     e2e_elapsed = time.perf_counter() - t0
 
+    # outputs of the LAST timed ingest step, as its caller receives them; copied
+    # now because --full's second window and the pinned result ring outlive it
+    dump = None
+    if args.dump_outputs:
+        dump = {
+            "checksums": pipe_e2e._e2e_sums.detach().cpu().numpy().astype("float64"),
+            "decisions": pipe_e2e._e2e_decisions.detach().cpu().numpy().astype("float32"),
+            "totals": [float(e2e_completed), float(e2e_denied)],
+        }
+
     # ---- window 2: in-HBM steady-state tick -------------------------------------
-    if use_gpu:
-        # sync-free timed window: stats fold into a device accumulator inside
-        # the captured tick (read ONCE after the closing barrier); per-step
-        # latency from hipEvents
-        pipe.reset_stats()
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-        t0 = time.perf_counter()
-        events[0].record()
-        for s in range(args.steps):
-            pipe.tick_async()
-            events[s + 1].record()
-        barrier()
-        tick_elapsed = time.perf_counter() - t0
-        tick_completed, tick_denied = pipe.collect_stats()
-        tick_steps = [events[s].elapsed_time(events[s + 1]) / 1000.0
-                      for s in range(args.steps)]
-    else:
-        t0 = time.perf_counter()
-        tick_steps = []
-        tick_completed = 0
-        tick_denied = 0
-        for _ in range(args.steps):
-            st = pipe.tick()
-            tick_steps.append(st.wall_s)
-            tick_completed += st.completed
-            tick_denied += st.denied
-        barrier()
-        tick_elapsed = time.perf_counter() - t0
+    tick_elapsed = tick_completed = tick_denied = 0
+    if pipe is not None:
+        if use_gpu:
+            # sync-free timed window: stats fold into a device accumulator inside
+            # the captured tick (read ONCE after the closing barrier); per-step
+            # latency from hipEvents
+            pipe.reset_stats()
+            events = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+            t0 = time.perf_counter()
+            events[0].record()
+            for s in range(args.steps):
+                pipe.tick_async()
+                events[s + 1].record()
+            barrier()
+            tick_elapsed = time.perf_counter() - t0
+            tick_completed, tick_denied = pipe.collect_stats()
+            tick_steps = [events[s].elapsed_time(events[s + 1]) / 1000.0
+                          for s in range(args.steps)]
+        else:
+            t0 = time.perf_counter()
+            tick_steps = []
+            tick_completed = 0
+            tick_denied = 0
+            for _ in range(args.steps):
+                st = pipe.tick()
+                tick_steps.append(st.wall_s)
+                tick_completed += st.completed
+                tick_denied += st.denied
+            barrier()
+            tick_elapsed = time.perf_counter() - t0
 
     # MAX elapsed over ranks; SUM of completed jobs over ranks
     def reduce_window(elapsed, completed):
@@ -286,12 +315,22 @@ def main() -> int:
 
     gc.enable()
     e2e_elapsed, e2e_completed = reduce_window(e2e_elapsed, e2e_completed)
-    tick_elapsed, tick_completed = reduce_window(tick_elapsed, tick_completed)
+    if pipe is not None:
+        tick_elapsed, tick_completed = reduce_window(tick_elapsed, tick_completed)
 
     e2e_jobs_per_sec = e2e_completed / e2e_elapsed
-    tick_jobs_per_sec = tick_completed / tick_elapsed
     ms_per_step = e2e_elapsed / args.steps * 1000.0
     p50_ms = statistics.median(e2e_steps) * 1000.0
+
+    if dump is not None:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        # one shard per rank; the single-rank names carry no suffix
+        suffix = f".rank{rank}" if world_size > 1 else ""
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"),
+                    np.asarray(arr, dtype=getattr(arr, "dtype", "float64")))
 
     baseline_sustained = 38234.0  # BASELINE.md peak-stress sustained jobs/s
     if rank == 0:
@@ -319,13 +358,15 @@ def main() -> int:
                 "workers_per_rank": args.workers,
                 "value_is": "end-to-end ingest rate (host encode + H2D + full "
                             "tick + result D2H all timed)",
-                "in_hbm_tick_jobs_per_s": round(tick_jobs_per_sec, 1),
-                "in_hbm_tick_ms_per_step": round(tick_elapsed / args.steps * 1000.0, 3),
                 "p50_dispatch_result_ms": round(p50_ms, 3),
                 "denied_jobs": e2e_denied + tick_denied,
                 "denied_excluded_from_value": True,
             },
         }
+        if pipe is not None:
+            out["config"]["in_hbm_tick_jobs_per_s"] = round(tick_completed / tick_elapsed, 1)
+            out["config"]["in_hbm_tick_ms_per_step"] = round(
+                tick_elapsed / args.steps * 1000.0, 3)
         print(json.dumps(out))
     if world_size > 1:
         dist.destroy_process_group()

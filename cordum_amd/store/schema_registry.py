@@ -46,6 +46,16 @@ def _type_ok(t: str, v: Any) -> bool:
     return True
 
 
+def _num(schema: Dict[str, Any], key: str) -> Optional[float]:
+    """A numeric keyword's value, or None when absent or malformed (a keyword
+    whose value has the wrong JSON type constrains nothing — schemas arrive
+    from API callers and must never crash the validator)."""
+    v = schema.get(key)
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return v
+    return None
+
+
 def validate_value(schema: Dict[str, Any], value: Any, path: str = "$",
                    root: Optional[Dict[str, Any]] = None) -> List[str]:
     errs: List[str] = []
@@ -70,43 +80,52 @@ def validate_value(schema: Dict[str, Any], value: Any, path: str = "$",
         if not any(_type_ok(x, value) for x in types):
             errs.append(f"{path}: expected {t}, got {type(value).__name__}")
             return errs
-    if "enum" in schema and value not in schema["enum"]:
+    if isinstance(schema.get("enum"), list) and value not in schema["enum"]:
         errs.append(f"{path}: not in enum {schema['enum']}")
     if "const" in schema and value != schema["const"]:
         errs.append(f"{path}: != const {schema['const']}")
     if isinstance(value, (int, float)) and not isinstance(value, bool):
-        if "minimum" in schema and value < schema["minimum"]:
+        if _num(schema, "minimum") is not None and value < schema["minimum"]:
             errs.append(f"{path}: {value} < minimum {schema['minimum']}")
-        if "maximum" in schema and value > schema["maximum"]:
+        if _num(schema, "maximum") is not None and value > schema["maximum"]:
             errs.append(f"{path}: {value} > maximum {schema['maximum']}")
-        if "exclusiveMinimum" in schema and value <= schema["exclusiveMinimum"]:
+        if _num(schema, "exclusiveMinimum") is not None and value <= schema["exclusiveMinimum"]:
             errs.append(f"{path}: {value} <= exclusiveMinimum {schema['exclusiveMinimum']}")
-        if "exclusiveMaximum" in schema and value >= schema["exclusiveMaximum"]:
+        if _num(schema, "exclusiveMaximum") is not None and value >= schema["exclusiveMaximum"]:
             errs.append(f"{path}: {value} >= exclusiveMaximum {schema['exclusiveMaximum']}")
-        if "multipleOf" in schema:
-            m = schema["multipleOf"]
-            q = value / m
-            if abs(q - round(q)) > 1e-9:
+        m = _num(schema, "multipleOf")
+        if m is not None:
+            try:
+                q = value / m
+                off = abs(q - round(q)) > 1e-9
+            except (ZeroDivisionError, OverflowError, ValueError):
+                off = False  # zero divisor / non-finite quotient: no constraint
+            if off:
                 errs.append(f"{path}: {value} not a multiple of {m}")
     if isinstance(value, str):
-        if "minLength" in schema and len(value) < schema["minLength"]:
+        if _num(schema, "minLength") is not None and len(value) < schema["minLength"]:
             errs.append(f"{path}: shorter than minLength {schema['minLength']}")
-        if "maxLength" in schema and len(value) > schema["maxLength"]:
+        if _num(schema, "maxLength") is not None and len(value) > schema["maxLength"]:
             errs.append(f"{path}: longer than maxLength {schema['maxLength']}")
-        if "pattern" in schema:
+        if isinstance(schema.get("pattern"), str):
             try:
                 if not re.search(schema["pattern"], value):
                     errs.append(f"{path}: does not match pattern {schema['pattern']}")
-            except re.error:
+            except (re.error, RecursionError, OverflowError):
                 pass
     if isinstance(value, dict):
-        props = schema.get("properties", {})
-        for req in schema.get("required", []):
+        props = schema.get("properties")
+        if not isinstance(props, dict):
+            props = {}
+        required = schema.get("required")
+        for req in required if isinstance(required, list) else []:
+            if not isinstance(req, str):
+                continue
             if req not in value:
                 errs.append(f"{path}: missing required property {req!r}")
-        if "minProperties" in schema and len(value) < schema["minProperties"]:
+        if _num(schema, "minProperties") is not None and len(value) < schema["minProperties"]:
             errs.append(f"{path}: fewer than minProperties {schema['minProperties']}")
-        if "maxProperties" in schema and len(value) > schema["maxProperties"]:
+        if _num(schema, "maxProperties") is not None and len(value) > schema["maxProperties"]:
             errs.append(f"{path}: more than maxProperties {schema['maxProperties']}")
         for k, v in value.items():
             if k in props:
@@ -130,9 +149,9 @@ def validate_value(schema: Dict[str, Any], value: Any, path: str = "$",
             elif isinstance(extra, dict):
                 for i in range(len(items), len(value)):
                     errs.extend(validate_value(extra, value[i], f"{path}[{i}]", root))
-        if "minItems" in schema and len(value) < schema["minItems"]:
+        if _num(schema, "minItems") is not None and len(value) < schema["minItems"]:
             errs.append(f"{path}: fewer than minItems {schema['minItems']}")
-        if "maxItems" in schema and len(value) > schema["maxItems"]:
+        if _num(schema, "maxItems") is not None and len(value) > schema["maxItems"]:
             errs.append(f"{path}: more than maxItems {schema['maxItems']}")
         if schema.get("uniqueItems"):
             seen = []
@@ -145,7 +164,7 @@ def validate_value(schema: Dict[str, Any], value: Any, path: str = "$",
         if not validate_value(schema["not"], value, path, root):
             errs.append(f"{path}: matches schema in 'not'")
     for comb, mode in (("anyOf", "any"), ("allOf", "all"), ("oneOf", "one")):
-        if comb in schema:
+        if isinstance(schema.get(comb), list):
             sub_errs = [validate_value(s, value, path, root) for s in schema[comb]]
             ok = [not e for e in sub_errs]
             if mode == "any" and not any(ok):

@@ -53,8 +53,8 @@ ROUTING = PoolRouting(
 
 def make_node(dispatch, policy=POLICY, workers=1):
     clock = ManualClock()
-    n = Node(clock=clock, routing=ROUTING, policy_yaml=policy,
-             dispatch=dispatch, backend="ref" if dispatch == "device" else None).start()
+    n = Node(clock=clock, routing=ROUTING, policy_yaml=policy, dispatch=dispatch,
+             device="cpu", backend="ref" if dispatch == "device" else None).start()
     for i in range(workers):
         n.add_worker(f"w{i}", topics=["job.default", "job.echo", "job.prod.deploy"])
     return n
@@ -320,7 +320,8 @@ def test_cancel_before_flush_drops_buffered_job():
     from cordum_amd.runtime.node import Node
     from cordum_amd.utils.clock import ManualClock
 
-    node = Node(clock=ManualClock(), dispatch="device", backend="ref").start()
+    node = Node(clock=ManualClock(), dispatch="device", device="cpu",
+                backend="ref").start()
     node.add_device_worker_pool(n_workers=2, topics=["job.default"])
     node.submit_job(JobRequest(job_id="cx-1", topic="job.default",
                                tenant_id="default"), context=b"{}")
@@ -346,7 +347,7 @@ def test_pending_replayer_redrives_device_engine():
     clock = ManualClock()
     routing = PoolRouting(topics={"job.default": ["default"]},
                           pools={"default": PoolProfile()})
-    node = Node(clock=clock, routing=routing, dispatch="device",
+    node = Node(clock=clock, routing=routing, dispatch="device", device="cpu",
                 backend="ref").start()
     node.submit_job(JobRequest(job_id="p1", topic="job.default",
                                tenant_id="default"), context=b"{}")

@@ -24,7 +24,7 @@ def node(request):
         topics={"job.default": ["default"], "job.echo": ["default"]},
         pools={"default": PoolProfile()},
     )
-    n = Node(clock=clock, routing=routing, dispatch=request.param,
+    n = Node(clock=clock, routing=routing, dispatch=request.param, device="cpu",
              backend="ref" if request.param == "device" else None).start()
     n.add_worker("w1", topics=["job.default", "job.echo"])
     return n

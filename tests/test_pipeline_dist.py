@@ -114,7 +114,10 @@ def test_bench_contract_torchrun_cpu(tmp_path):
     from pathlib import Path
 
     repo = Path(__file__).resolve().parent.parent
-    env = dict(os.environ, PYTHONPATH=str(repo))
+    # CPU/gloo is what is under test: hide any GPU, or two ranks would share
+    # one device over RCCL, which RCCL rejects
+    env = dict(os.environ, PYTHONPATH=str(repo),
+               HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     res = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -131,6 +134,55 @@ def test_bench_contract_torchrun_cpu(tmp_path):
     assert out["value"] > 0
     assert out["scaling"] == "weak"
     assert out["config"]["global_batch"] == 512
+
+
+def test_bench_plain_vs_full_and_dump_outputs_cpu(tmp_path):
+    """A plain run times and reports the ingest window only; --full adds the
+    in-HBM tick window to the same line. --dump-outputs writes the last timed
+    step's results as float .npy, identical from run to run for the same
+    arguments (the second window must not disturb them)."""
+    import subprocess
+    from pathlib import Path
+
+    import numpy as np
+
+    repo = Path(__file__).resolve().parent.parent
+    # the CPU validation path (--allow-cpu) is what is under test: hide any GPU
+    env = dict(os.environ, PYTHONPATH=str(repo),
+               HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+
+    def bench(*extra):
+        res = subprocess.run(
+            [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--batch", "256", "--workers", "16", "--rules", "64",
+             "--allow-cpu", *extra],
+            cwd=str(repo), env=env, capture_output=True, text=True, timeout=150,
+        )
+        assert res.returncode == 0, res.stdout + res.stderr
+        return json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+
+    plain = bench("--dump-outputs", str(tmp_path / "a"))
+    full = bench("--full", "--dump-outputs", str(tmp_path / "b"))
+    for out in (plain, full):
+        assert out["metric"] == "jobs dispatched/sec (whole node)"
+        assert out["unit"] == "jobs/s" and out["higher_is_better"] is True
+        assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["dtype"].startswith("int64-bitset/int32")
+    assert "in_hbm_tick_jobs_per_s" not in plain["config"]
+    assert full["config"]["in_hbm_tick_jobs_per_s"] > 0
+    assert full["config"]["in_hbm_tick_ms_per_step"] > 0
+
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["checksums.npy", "decisions.npy", "totals.npy"]
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64)
+        assert np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "checksums.npy").shape == (256,)
+    assert np.load(tmp_path / "a" / "decisions.npy").shape == (256,)
+    completed, denied = np.load(tmp_path / "a" / "totals.npy")
+    assert completed > 0 and completed + denied <= 3 * 256
 
 
 def _worker_async(rank, world, port, result_dir):

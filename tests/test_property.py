@@ -459,6 +459,38 @@ def test_schema_validator_never_crashes(schema, value):
     assert isinstance(errs, list)
 
 
+def test_schema_validator_ignores_malformed_keywords():
+    """Every keyword given a value of each wrong JSON type, against a value
+    of every JSON type: no exception, and a malformed keyword constrains
+    nothing (the random search above reaches these pairs only rarely)."""
+    from cordum_amd.store.schema_registry import validate_value
+
+    keywords = ["type", "enum", "const", "minimum", "maximum", "exclusiveMinimum",
+                "exclusiveMaximum", "multipleOf", "minLength", "maxLength",
+                "pattern", "properties", "required", "minProperties",
+                "maxProperties", "additionalProperties", "items",
+                "additionalItems", "minItems", "maxItems", "uniqueItems",
+                "not", "anyOf", "allOf", "oneOf", "$ref"]
+    junk = [None, True, False, 0, -1, 3, 0.0, 2.5, float("nan"), float("inf"),
+            10 ** 400, "", "a", "(", "#/nope", [], [1], ["a", 1, None], [[]],
+            [{}], {}, {"a": 1}, {"a": {"type": 5}}]
+    values = [None, True, 0, 7, 2.5, float("nan"), float("inf"), 10 ** 400, "",
+              "abc", [], [1, 1], [{"a": 1}], {}, {"a": 1, "b": [2]}]
+    for kw in keywords:
+        for j in junk:
+            for v in values:
+                errs = validate_value({kw: j}, v)
+                assert isinstance(errs, list), (kw, j, v)
+    # wrong-typed keyword values are ignored, not treated as violated
+    assert validate_value({"minimum": "5", "maxLength": None, "required": 3,
+                           "enum": "abc", "anyOf": 1, "pattern": 7,
+                           "properties": [], "multipleOf": 0}, 1) == []
+    assert validate_value({"required": [1, None, "a"]}, {"a": 0}) == []
+    # well-formed keywords next to malformed ones still apply
+    assert validate_value({"minimum": 5, "maximum": "x"}, 1)
+    assert validate_value({"enum": [1, 2], "anyOf": 0}, 3)
+
+
 # --- bus NAK redelivery -------------------------------------------------------
 
 

@@ -199,7 +199,12 @@ def test_external_worker_over_tcp_bridge(tmp_path):
     import json
 
     port = free_port()
-    env = dict(os.environ, PYTHONPATH=str(REPO), CORDUM_BRIDGE_PORT="0")
+    # host dispatch with one in-process worker, whatever the machine: routing
+    # is per pool with ties broken by worker id, and the external worker wins
+    # the tie only against the host engine's "worker-N" (on a GPU host the
+    # default is device dispatch, whose pool workers would take the job)
+    env = dict(os.environ, PYTHONPATH=str(REPO), CORDUM_BRIDGE_PORT="0",
+               CORDUM_DISPATCH="host")
     proc = subprocess.Popen(
         [sys.executable, "-m", "cordum_amd.cli.cordumctl", "serve",
          "--port", str(port), "--workers", "1"],
