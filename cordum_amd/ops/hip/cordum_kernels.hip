@@ -951,8 +951,14 @@ __global__ __launch_bounds__(BLOCK) void echo_worker_indexed_kernel(
 // bitset-vs-MFMA verdict.
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
-    const signed char* __restrict__ a_pack,   // [Jt][9][64][16]
+// The rule scan for TJ consecutive 16-job tiles held by one wave, shared by
+// the kernels below, which differ only in where the lane's A fragments come
+// from. With TJ > 1 one B-fragment load, one cards gather and one tile_dims
+// read serve TJ MFMAs: the scan is bound by those dependent loads, not by
+// the matrix cores (19 G int8 ops per tick are a few microseconds of MFMA).
+template <int TJ>
+__device__ __forceinline__ void mfma_first_match_tiles(
+    const v4i (&afrag)[TJ][9],
     const signed char* __restrict__ b_pack,   // [Rt][9][64][16]
     const int* __restrict__ cards,            // [Rt*16][9]
     const signed char* __restrict__ rule_secrets, // [Rt*16]
@@ -963,25 +969,23 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
 {
     const int wave = threadIdx.x / WAVE;      // 4 waves per block
     const int lane = threadIdx.x % WAVE;
-    const int jt = blockIdx.x;                // one job tile per block
+    const int jt0 = blockIdx.x * TJ;          // TJ job tiles per block
     const int Rt = (R + 15) / 16;
     const int chunk_begin = blockIdx.y * tiles_per_chunk;
     const int chunk_end = min(Rt, chunk_begin + tiles_per_chunk);
 
-    // A fragments for the 9 dims: lane-linear 16 B loads
-    v4i afrag[9];
-    #pragma unroll
-    for (int d = 0; d < 9; ++d)
-        afrag[d] = *(const v4i*)&a_pack[(((size_t)jt * 9 + d) * 64 + lane) * 16];
-
     const int row_base = (lane >> 4) * 4;     // 4 job rows per lane
     const int col = lane & 15;                // rule column
-    int best[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
-    unsigned char jsec[4];
+    int best[TJ][4];
+    unsigned char jsec[TJ][4];
     #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int job = jt * 16 + row_base + r;
-        jsec[r] = (job < J) ? job_secrets[job] : 0;
+    for (int t = 0; t < TJ; ++t) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int job = (jt0 + t) * 16 + row_base + r;
+            best[t][r] = INT_MAX;
+            jsec[t][r] = (job < J) ? job_secrets[job] : 0;
+        }
     }
 
     // early-exit checks only pay when each wave scans enough rule tiles
@@ -995,24 +999,35 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
         const unsigned dmask = (unsigned)tile_dims[rt];
         const int rule = rt * 16 + col;
         const signed char rsec = rule_secrets[rule];
-        bool ok[4] = {true, true, true, true};
+        bool ok[TJ][4];
+        #pragma unroll
+        for (int t = 0; t < TJ; ++t) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) ok[t][r] = true;
+        }
         #pragma unroll
         for (int d = 0; d < 9; ++d) {
             if (!(dmask & (1u << d))) continue;
             const v4i bfrag = *(const v4i*)&b_pack[(((size_t)rt * 9 + d) * 64 + lane) * 16];
-            v4i zero = {0, 0, 0, 0};
-            const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(afrag[d], bfrag, zero, 0, 0, 0);
             const int card = cards[rule * 9 + d];
             #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (d < 7) ok[r] &= (card == 0) | (acc[r] > 0);   // any-of
-                else       ok[r] &= (acc[r] == card);             // all-of
+            for (int t = 0; t < TJ; ++t) {
+                v4i zero = {0, 0, 0, 0};
+                const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(afrag[t][d], bfrag, zero, 0, 0, 0);
+                #pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (d < 7) ok[t][r] &= (card == 0) | (acc[r] > 0);   // any-of
+                    else       ok[t][r] &= (acc[r] == card);             // all-of
+                }
             }
         }
         #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool pass = ok[r] & ((rsec < 0) | (rsec == (signed char)jsec[r]));
-            if (pass && rule < R) best[r] = min(best[r], rule);
+        for (int t = 0; t < TJ; ++t) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool pass = ok[t][r] & ((rsec < 0) | (rsec == (signed char)jsec[t][r]));
+                if (pass && rule < R) best[t][r] = min(best[t][r], rule);
+            }
         }
 
         // first-match early exit, adaptive: stop once every job row of the
@@ -1027,14 +1042,17 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
         if (do_exit && ((rt >> 2) & 3) == 3) {
             bool all_matched = true;
             #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int job = jt * 16 + row_base + r;
-                if (job < J)
-                    best[r] = min(best[r], __hip_atomic_load(&out_first[job],
-                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                const unsigned long long m = __ballot(best[r] != INT_MAX);
-                all_matched &= ((m & 0xFFFFull) != 0) & (((m >> 16) & 0xFFFFull) != 0)
-                             & (((m >> 32) & 0xFFFFull) != 0) & (((m >> 48) & 0xFFFFull) != 0);
+            for (int t = 0; t < TJ; ++t) {
+                #pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int job = (jt0 + t) * 16 + row_base + r;
+                    if (job < J)
+                        best[t][r] = min(best[t][r], __hip_atomic_load(&out_first[job],
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    const unsigned long long m = __ballot(best[t][r] != INT_MAX);
+                    all_matched &= ((m & 0xFFFFull) != 0) & (((m >> 16) & 0xFFFFull) != 0)
+                                 & (((m >> 32) & 0xFFFFull) != 0) & (((m >> 48) & 0xFFFFull) != 0);
+                }
             }
             if (all_matched) break;
         }
@@ -1042,20 +1060,85 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
 
     // min across the 16 rule columns (lanes sharing the same lane>>4 group)
     #pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
+    for (int t = 0; t < TJ; ++t) {
         #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int other = __shfl_xor(best[r], off, WAVE);
-            if ((lane & 15) < 16) best[r] = min(best[r], other);
+        for (int off = 8; off > 0; off >>= 1) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r)
+                best[t][r] = min(best[t][r], __shfl_xor(best[t][r], off, WAVE));
+        }
+        if ((lane & 15) == 0) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int job = (jt0 + t) * 16 + row_base + r;
+                if (job < J && best[t][r] != INT_MAX) atomicMin(&out_first[job], best[t][r]);
+            }
         }
     }
-    if ((lane & 15) == 0) {
+}
+
+__global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_kernel(
+    const signed char* __restrict__ a_pack,   // [Jt][9][64][16]
+    const signed char* __restrict__ b_pack,
+    const int* __restrict__ cards,
+    const signed char* __restrict__ rule_secrets,
+    const unsigned char* __restrict__ job_secrets,
+    const int* __restrict__ tile_dims,
+    int* __restrict__ out_first,
+    int J, int R, int tiles_per_chunk)
+{
+    const int lane = threadIdx.x % WAVE;
+    const int jt = blockIdx.x;
+    // A fragments for the 9 dims: lane-linear 16 B loads
+    v4i afrag[1][9];
+    #pragma unroll
+    for (int d = 0; d < 9; ++d)
+        afrag[0][d] = *(const v4i*)&a_pack[(((size_t)jt * 9 + d) * 64 + lane) * 16];
+    mfma_first_match_tiles<1>(afrag, b_pack, cards, rule_secrets, job_secrets,
+                              tile_dims, out_first, J, R, tiles_per_chunk);
+}
+
+// K1 straight from the staged bit words: each lane expands its own A
+// fragments in registers (the bytes pack_jobs_mfma_kernel would have
+// written: lane -> job row lane&15, 16-bit slice lane>>4 of the dim's word,
+// one int8 per bit). Saves the pack launch and the write-then-read of the
+// [Jt,9,64,16] pack (9.4 MB per tick at 16384 jobs) for 9 word loads.
+// TJ = job tiles per wave (register blocking, see mfma_first_match_tiles).
+template <int TJ>
+__global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_bits_kernel(
+    const long long* __restrict__ any_bits,   // [J,7] (1-word vocab)
+    const long long* __restrict__ all_bits,   // [J,2]
+    const signed char* __restrict__ b_pack,
+    const int* __restrict__ cards,
+    const signed char* __restrict__ rule_secrets,
+    const unsigned char* __restrict__ job_secrets,
+    const int* __restrict__ tile_dims,
+    int* __restrict__ out_first,
+    int J, int R, int tiles_per_chunk)
+{
+    const int lane = threadIdx.x % WAVE;
+    const int shift = (lane >> 4) * 16;
+    v4i afrag[TJ][9];
+    #pragma unroll
+    for (int t = 0; t < TJ; ++t) {
+        const int job = (blockIdx.x * TJ + t) * 16 + (lane & 15);
         #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int job = jt * 16 + row_base + r;
-            if (job < J && best[r] != INT_MAX) atomicMin(&out_first[job], best[r]);
+        for (int d = 0; d < 9; ++d) {
+            unsigned long long w = 0;
+            if (job < J)
+                w = (unsigned long long)(d < 7 ? any_bits[(size_t)job * 7 + d]
+                                               : all_bits[(size_t)job * 2 + (d - 7)]);
+            const unsigned int slice = (unsigned int)(w >> shift) & 0xFFFFu;
+            // nibble -> 4 bytes of 0/1: the multiply puts bit b at 7b+b, the
+            // mask keeps bit b of the nibble at byte b (little-endian =
+            // element order)
+            #pragma unroll
+            for (int q = 0; q < 4; ++q)
+                afrag[t][d][q] = (int)((((slice >> (4 * q)) & 0xFu) * 0x00204081u) & 0x01010101u);
         }
     }
+    mfma_first_match_tiles<TJ>(afrag, b_pack, cards, rule_secrets, job_secrets,
+                               tile_dims, out_first, J, R, tiles_per_chunk);
 }
 
 // ---------------------------------------------------------------------------
@@ -1349,6 +1432,193 @@ __global__ __launch_bounds__(BLOCK) void load_feedback_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Fused single-GPU tick: prologue | K2 pick | K1 | gate+route | finish.
+// The kernels above stay as they are (the eager and padded ticks call them,
+// and tests/test_gpu_tick_fusion.py holds the fused ones to them). Ten of
+// the old tick's twelve launches ran 4.4-8.8 us each over a few thousand
+// threads of work (profiles/r49_e2e_overlap_ktrace_stats.txt): launch tax.
+// ---------------------------------------------------------------------------
+
+// begin_tick_first + worker_precompute_into in one launch. w_key is written
+// in full (the eager order refresh sorts it); `first` may be null.
+__global__ __launch_bounds__(BLOCK) void tick_prologue_kernel(
+    unsigned char* __restrict__ states, int B,
+    int* __restrict__ counts, int ncounts,
+    int* __restrict__ first,
+    const int* __restrict__ w_active,
+    const int* __restrict__ w_maxp,
+    const float* __restrict__ w_cpu,
+    const float* __restrict__ w_gpu,
+    unsigned long long* __restrict__ w_key, int NW)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < B) {
+        states[i] = 1;  // PENDING
+        if (first != nullptr) first[i] = INT_MAX;
+    }
+    if (i < ncounts) counts[i] = 0;
+    if (i < NW) {
+        const int active = w_active[i], maxp = w_maxp[i];
+        const float cpu = w_cpu[i], gpu = w_gpu[i];
+        bool over = false;
+        if (maxp > 0 && (float)active / (float)maxp >= 0.9f) over = true;
+        if (cpu >= 90.f || gpu >= 90.f) over = true;
+        if (over) {
+            w_key[i] = 0xfffffffe00000000ull | (unsigned int)i;  // OVERLOADED
+        } else {
+            const float score = (float)active + cpu * 0.01f + gpu * 0.01f;
+            w_key[i] = score_key(score, i);
+        }
+    }
+}
+
+// policy_gate_full + compact_routable_spread in one launch, one thread per
+// job slot: decision, DENIED transition + DLQ append, allowed append, the
+// spread / exact worker pick and the routable append. The compacted lists
+// come out in a different (still unspecified) order; per-slot outputs are
+// those of the two kernels it replaces. Also zeroes the per-tick local-load
+// accumulator (the prologue has read it by now) for the finish kernel.
+__global__ __launch_bounds__(BLOCK) void gate_route_kernel(
+    const int* __restrict__ first,            // [J]
+    const signed char* __restrict__ decisions, // [R]
+    signed char* __restrict__ out_decision,   // [J]
+    int* __restrict__ denied_slots, int* __restrict__ denied_count,
+    int* __restrict__ allowed_slots, int* __restrict__ allowed_count,
+    unsigned char* __restrict__ states,
+    long long* __restrict__ deadlines,
+    int* __restrict__ dlq_ring, int* __restrict__ dlq_head, int ring_size,
+    const int* __restrict__ pick,             // [J] exact least-loaded pick
+    const int* __restrict__ order,            // [NW] workers by key asc
+    const int* __restrict__ valid_count,      // [1] non-overloaded workers
+    const long long* __restrict__ j_poolmask,
+    const long long* __restrict__ j_labels,
+    long long full_mask, int K,
+    int* __restrict__ routable_slots, int* __restrict__ routable_widx,
+    int* __restrict__ routable_count,
+    int* __restrict__ extra_zero, int n_extra,
+    int J, int R)
+{
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    const int lane = threadIdx.x % WAVE;
+    if (j < n_extra) extra_zero[j] = 0;
+    const bool live = j < J;
+    signed char d = 0;
+    if (live) {
+        const int r = first[j];
+        d = (r >= 0 && r < R) ? decisions[r] : (signed char)1;  // default allow
+        out_decision[j] = d;
+    }
+    const bool allowed = live && (d == 1 || d == 5);
+    const int apos = wave_append_slot(allowed, allowed_count, lane);
+    if (apos >= 0) allowed_slots[apos] = j;
+    const bool denied = live && !allowed;
+    const int dpos = wave_append_slot(denied, denied_count, lane);
+    if (dpos >= 0) denied_slots[dpos] = j;
+    bool dlq = false;
+    if (denied) {
+        const unsigned char from = states[j];
+        if (d_transition_lut[from * N_STATES + 10]) {  // -> DENIED
+            states[j] = 10;
+            deadlines[j] = (long long)0x7fffffffffffffffLL;
+            dlq = true;
+        }
+    }
+    const int rpos = wave_append_slot(dlq, dlq_head, lane);
+    if (rpos >= 0) dlq_ring[rpos % ring_size] = j;
+    // route: K2c spread for unconstrained jobs, exact scan pick otherwise
+    int w = -1;
+    if (allowed) {
+        if (j_labels[j] == 0 && j_poolmask[j] == full_mask) {
+            const int V = min(*valid_count, K);
+            w = (V > 0) ? order[j % V] : pick[j];
+        } else {
+            w = pick[j];
+        }
+    }
+    const int pos = wave_append_slot(w >= 0, routable_count, lane);
+    if (pos >= 0) {
+        routable_slots[pos] = j;
+        routable_widx[pos] = w;
+    }
+}
+
+// echo_execute_indexed_dyn + apply_transitions_chain_dyn + load_feedback +
+// accumulate_counts in one launch. routable_count is final before this
+// kernel starts. One wave echoes one routed job and its lane 0 marches that
+// job's state chain; thread i of the grid (there are 64 per routed job, so
+// i < count is always covered) takes entry i of the load histogram with the
+// same match-any aggregation as load_feedback_kernel; thread t < ncounts of
+// block 0 folds the tick counters.
+__global__ __launch_bounds__(BLOCK) void tick_finish_kernel(
+    const unsigned int* __restrict__ ctx_arena,
+    const int* __restrict__ slots,            // routable_slots
+    const int* __restrict__ widx,             // routable_widx
+    const int* __restrict__ count,            // [1] routable_count
+    unsigned int* __restrict__ res_arena,
+    unsigned int* __restrict__ res_sum,
+    int stride,
+    unsigned char* __restrict__ states,
+    int* __restrict__ attempts,
+    long long* __restrict__ deadlines,
+    int to0, int to1, int to2, int to3,       // -1 = unused
+    int* __restrict__ w_active_local,         // [NWL] zeroed by gate_route
+    int nwl, int my_rank,
+    const int* __restrict__ counts, long long* __restrict__ acc, int ncounts)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    const int w = i / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    const int n = *count;
+    if (blockIdx.x == 0 && threadIdx.x < ncounts)
+        acc[threadIdx.x] += (long long)counts[threadIdx.x];
+
+    // load histogram: one thread per routed entry, grouped by equal bin
+    bool live = i < n;
+    int bin = -1;
+    if (live) {
+        const int wk = widx[i];
+        if (wk / nwl == my_rank) bin = wk % nwl;
+        else live = false;
+    }
+    unsigned long long pending = __ballot(live);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int leader_bin = __shfl(bin, leader, WAVE);
+        const unsigned long long same = __ballot(live && bin == leader_bin);
+        if (lane == leader) atomicAdd(&w_active_local[leader_bin], __popcll(same));
+        pending &= ~same;
+    }
+
+    if (w >= n) return;  // wave-uniform
+    const int slot = slots[w];
+    const size_t basep = (size_t)slot * stride;
+    unsigned int sum = 0;
+    for (int k = lane; k < stride; k += WAVE) {
+        const unsigned int v = ctx_arena[basep + k];
+        res_arena[basep + k] = v;
+        sum += v;
+    }
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        sum += __shfl_down(sum, off, WAVE);
+    if (lane == 0) {
+        res_sum[slot] = sum;
+        unsigned char from = states[slot];
+        const int chain[4] = {to0, to1, to2, to3};
+        #pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (chain[c] < 0) break;
+            const unsigned char to = (unsigned char)chain[c];
+            if (!d_transition_lut[from * N_STATES + to]) break;
+            if (to == 3 && from != 3) attempts[slot] += 1;
+            from = to;
+        }
+        states[slot] = from;
+        if (from >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
+    }
+}
+
 
 // ---------------------------------------------------------------------------
 // Padded cross-rank dispatch (multi-GPU path): fixed-capacity per-destination
@@ -1628,6 +1898,8 @@ __global__ __launch_bounds__(BLOCK) void pack_jobs_mfma_kernel(
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+
+#include "synthetic_encode.h"
 
 #define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be on device")
 #define CHECK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
@@ -2055,6 +2327,142 @@ void load_feedback(torch::Tensor routable_widx, torch::Tensor count,
         w_active_local.data_ptr<int>(), (int)nwl, (int)my_rank);
 }
 
+// -- fused single-GPU tick (5 launches: these four + least_loaded_pick_into) --
+void tick_prologue(torch::Tensor states, torch::Tensor counts,
+                   c10::optional<torch::Tensor> first,
+                   torch::Tensor w_active, torch::Tensor w_maxp,
+                   torch::Tensor w_cpu, torch::Tensor w_gpu, torch::Tensor out_keys)
+{
+    CHECK_DEV(states);
+    const int B = (int)states.size(0);
+    const int n = (int)counts.size(0);
+    const int NW = (int)out_keys.size(0);
+    TORCH_CHECK(w_active.size(0) == NW && w_maxp.size(0) == NW &&
+                w_cpu.size(0) == NW && w_gpu.size(0) == NW, "worker table size mismatch");
+    TORCH_CHECK(!first.has_value() || first->size(0) == B, "first must be [B]");
+    const int blocks = (std::max(std::max(B, n), std::max(NW, 1)) + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(tick_prologue_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        states.data_ptr<uint8_t>(), B, counts.data_ptr<int>(), n,
+        first.has_value() ? first->data_ptr<int>() : (int*)nullptr,
+        w_active.data_ptr<int>(), w_maxp.data_ptr<int>(),
+        w_cpu.data_ptr<float>(), w_gpu.data_ptr<float>(),
+        (unsigned long long*)out_keys.data_ptr<int64_t>(), NW);
+}
+
+void policy_first_match_mfma_bits_into(
+    torch::Tensor any_bits, torch::Tensor all_bits,
+    torch::Tensor b_pack, torch::Tensor cards,
+    torch::Tensor rule_secrets, torch::Tensor job_secrets,
+    torch::Tensor tile_dims, int64_t n_rules, torch::Tensor out, int64_t job_tiles)
+{
+    CHECK_DEV(any_bits); CHECK_DEV(b_pack);
+    CHECK_CONTIG(any_bits); CHECK_CONTIG(all_bits);
+    TORCH_CHECK(job_tiles == 1 || job_tiles == 2, "job_tiles must be 1 or 2");
+    TORCH_CHECK(any_bits.dim() == 3 && any_bits.size(1) == 7 && any_bits.size(2) == 1 &&
+                all_bits.dim() == 3 && all_bits.size(1) == 2 && all_bits.size(2) == 1,
+                "MFMA K1 needs the 1-word vocab: any [J,7,1], all [J,2,1]");
+    const int J = (int)any_bits.size(0), R = (int)n_rules;
+    TORCH_CHECK(all_bits.size(0) == J && job_secrets.size(0) >= J && out.size(0) >= J,
+                "job tensors must cover J");
+    const int TJ = (int)job_tiles;
+    const int Jt = ((J + 15) / 16 + TJ - 1) / TJ;   // blocks of TJ job tiles
+    const int Rt = (R + 15) / 16;
+    if (J == 0 || R == 0) return;
+    TORCH_CHECK(b_pack.size(0) >= Rt && tile_dims.size(0) >= Rt &&
+                rule_secrets.size(0) >= Rt * 16 && cards.size(0) >= Rt * 16,
+                "rule pack smaller than n_rules");
+    int nchunks = std::max(1, std::min((Rt + 3) / 4, std::max(1, 2048 / std::max(Jt, 1))));
+    const int tiles_per_chunk = (Rt + nchunks - 1) / nchunks;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(Jt, nchunks), dim3(BLOCK), 0, cur_stream(),
+            (const long long*)any_bits.data_ptr<int64_t>(),
+            (const long long*)all_bits.data_ptr<int64_t>(),
+            (const signed char*)b_pack.data_ptr<int8_t>(),
+            cards.data_ptr<int>(),
+            (const signed char*)rule_secrets.data_ptr<int8_t>(),
+            job_secrets.data_ptr<uint8_t>(),
+            tile_dims.data_ptr<int>(),
+            out.data_ptr<int>(), J, R, tiles_per_chunk);
+    };
+    // 4 tiles per wave was tried and dropped: 215 VGPRs, 2 waves/SIMD, 41 us
+    // against 27 us for 2 (profiles/r51_k1_register_blocking.txt)
+    if (TJ == 2) launch(policy_first_match_mfma_bits_kernel<2>);
+    else launch(policy_first_match_mfma_bits_kernel<1>);
+}
+
+void gate_route(torch::Tensor first, torch::Tensor decisions, torch::Tensor out_decision,
+                torch::Tensor denied_slots, torch::Tensor denied_count,
+                torch::Tensor allowed_slots, torch::Tensor allowed_count,
+                torch::Tensor states, torch::Tensor deadlines,
+                torch::Tensor dlq_ring, torch::Tensor dlq_head,
+                torch::Tensor pick, torch::Tensor order, torch::Tensor valid_count,
+                torch::Tensor j_poolmask, torch::Tensor j_labels,
+                int64_t full_mask, int64_t K,
+                torch::Tensor routable_slots, torch::Tensor routable_widx,
+                torch::Tensor routable_count, torch::Tensor extra_zero)
+{
+    CHECK_DEV(first);
+    const int J = (int)first.size(0);
+    TORCH_CHECK(out_decision.size(0) >= J && denied_slots.size(0) >= J &&
+                allowed_slots.size(0) >= J && states.size(0) >= J &&
+                deadlines.size(0) >= J && pick.size(0) >= J &&
+                j_poolmask.size(0) >= J && j_labels.size(0) >= J &&
+                routable_slots.size(0) >= J && routable_widx.size(0) >= J,
+                "per-job tensors must cover J");
+    // the spread reads order[j % min(valid_count, K)]
+    TORCH_CHECK(K <= order.size(0), "K exceeds the order table");
+    const int n_extra = (int)extra_zero.size(0);
+    const int blocks = (std::max(std::max(J, n_extra), 1) + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(gate_route_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        first.data_ptr<int>(), (const signed char*)decisions.data_ptr<int8_t>(),
+        (signed char*)out_decision.data_ptr<int8_t>(),
+        denied_slots.data_ptr<int>(), denied_count.data_ptr<int>(),
+        allowed_slots.data_ptr<int>(), allowed_count.data_ptr<int>(),
+        states.data_ptr<uint8_t>(), (long long*)deadlines.data_ptr<int64_t>(),
+        dlq_ring.data_ptr<int>(), dlq_head.data_ptr<int>(), (int)dlq_ring.size(0),
+        pick.data_ptr<int>(), order.data_ptr<int>(), valid_count.data_ptr<int>(),
+        (const long long*)j_poolmask.data_ptr<int64_t>(),
+        (const long long*)j_labels.data_ptr<int64_t>(),
+        (long long)full_mask, (int)K,
+        routable_slots.data_ptr<int>(), routable_widx.data_ptr<int>(),
+        routable_count.data_ptr<int>(),
+        extra_zero.data_ptr<int>(), n_extra,
+        J, (int)decisions.size(0));
+}
+
+void tick_finish(torch::Tensor ctx_arena, torch::Tensor routable_slots,
+                 torch::Tensor routable_widx, torch::Tensor routable_count,
+                 torch::Tensor res_arena, torch::Tensor res_sum, int64_t stride,
+                 torch::Tensor states, torch::Tensor attempts, torch::Tensor deadlines,
+                 std::vector<int64_t> chain,
+                 torch::Tensor w_active_local, int64_t nwl, int64_t my_rank,
+                 torch::Tensor counts, torch::Tensor acc, int64_t capacity)
+{
+    CHECK_DEV(ctx_arena);
+    TORCH_CHECK(capacity <= routable_slots.size(0) && capacity <= routable_widx.size(0),
+                "capacity exceeds the routable lists");
+    TORCH_CHECK(ctx_arena.numel() >= capacity * stride && res_arena.numel() >= capacity * stride &&
+                res_sum.size(0) >= capacity && states.size(0) >= capacity,
+                "arenas must cover capacity slots");
+    TORCH_CHECK(nwl > 0 && w_active_local.size(0) >= nwl, "w_active_local must be [nwl]");
+    TORCH_CHECK(acc.size(0) >= counts.size(0) && counts.size(0) <= BLOCK, "acc must cover counts");
+    int to[4] = {-1, -1, -1, -1};
+    for (size_t c = 0; c < chain.size() && c < 4; ++c) to[c] = (int)chain[c];
+    const int waves_per_block = BLOCK / WAVE;
+    const int blocks = (std::max((int)capacity, 1) + waves_per_block - 1) / waves_per_block;
+    hipLaunchKernelGGL(tick_finish_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        (const unsigned int*)ctx_arena.data_ptr<int32_t>(),
+        routable_slots.data_ptr<int>(), routable_widx.data_ptr<int>(),
+        routable_count.data_ptr<int>(),
+        (unsigned int*)res_arena.data_ptr<int32_t>(),
+        (unsigned int*)res_sum.data_ptr<int32_t>(), (int)stride,
+        states.data_ptr<uint8_t>(), attempts.data_ptr<int>(),
+        (long long*)deadlines.data_ptr<int64_t>(),
+        to[0], to[1], to[2], to[3],
+        w_active_local.data_ptr<int>(), (int)nwl, (int)my_rank,
+        counts.data_ptr<int>(), (long long*)acc.data_ptr<int64_t>(), (int)counts.size(0));
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> run_readiness(
     torch::Tensor step_state, torch::Tensor deps_mask, torch::Tensor n_steps,
     torch::Tensor run_active, int64_t cap)
@@ -2414,6 +2822,60 @@ void synthetic_fresh(torch::Tensor any_bits,   // [B,7,W] int64 (host)
     }
 }
 
+// Whole host-side batch preparation in one GIL-free call: the four synthetic
+// dims exactly as synthetic_fresh draws them (synthetic_fresh stays the
+// oracle) plus the per-step stamp of payload word 0. The loop lives in
+// synthetic_encode.h (blocked hash, runtime-picked ISA, optional 2-way split
+// over a thread the call owns).
+void synthetic_fresh_stamped(torch::Tensor any_bits,   // [B,7,W] int64 (host)
+                             torch::Tensor all_bits,   // [B,2,W] int64 (host)
+                             torch::Tensor tenant_lut, torch::Tensor topic_lut,
+                             torch::Tensor risk_lut, torch::Tensor req_lut,
+                             int64_t seed, int64_t step,
+                             int64_t dim_tenant, int64_t dim_topic, int64_t dim_risk,
+                             int64_t all_requires,
+                             c10::optional<torch::Tensor> payload,  // [B*words] int32 (host)
+                             int64_t payload_words,
+                             int64_t threads, int64_t isa_cap)
+{
+    TORCH_CHECK(!any_bits.is_cuda() && !all_bits.is_cuda(),
+                "synthetic_fresh_stamped is a host encoder");
+    CHECK_CONTIG(any_bits); CHECK_CONTIG(all_bits);
+    CHECK_CONTIG(tenant_lut); CHECK_CONTIG(topic_lut);
+    CHECK_CONTIG(risk_lut); CHECK_CONTIG(req_lut);
+    cordum_enc::EncodeJob a;
+    a.B = any_bits.size(0);
+    a.W = any_bits.size(2);
+    a.V = tenant_lut.size(0);
+    TORCH_CHECK(any_bits.size(1) == 7 && all_bits.size(0) == a.B &&
+                all_bits.size(1) == 2 && all_bits.size(2) == a.W, "bad batch shape");
+    for (const torch::Tensor* l : {&tenant_lut, &topic_lut, &risk_lut, &req_lut})
+        TORCH_CHECK(l->size(0) == a.V && l->size(1) == a.W, "bad LUT shape");
+    TORCH_CHECK(dim_tenant >= 0 && dim_tenant < 7 && dim_topic >= 0 && dim_topic < 7 &&
+                dim_risk >= 0 && dim_risk < 7 && all_requires >= 0 && all_requires < 2,
+                "dim index out of range");
+    a.any = any_bits.data_ptr<int64_t>();
+    a.all = all_bits.data_ptr<int64_t>();
+    a.tenant_lut = tenant_lut.data_ptr<int64_t>();
+    a.topic_lut = topic_lut.data_ptr<int64_t>();
+    a.risk_lut = risk_lut.data_ptr<int64_t>();
+    a.req_lut = req_lut.data_ptr<int64_t>();
+    a.seed = (uint64_t)seed;
+    a.step = (uint64_t)step;
+    a.dim_tenant = (int)dim_tenant;
+    a.dim_topic = (int)dim_topic;
+    a.dim_risk = (int)dim_risk;
+    a.all_requires = (int)all_requires;
+    a.payload = nullptr;
+    a.payload_words = payload_words;
+    if (payload.has_value()) {
+        TORCH_CHECK(!payload->is_cuda() && payload->is_contiguous() &&
+                    payload->scalar_type() == torch::kInt32 && payload_words > 0 &&
+                    payload->numel() >= a.B * payload_words, "bad payload ring buffer");
+        a.payload = payload->data_ptr<int32_t>();
+    }
+    cordum_enc::encode_batch(a, (int)threads, (int)isa_cap);
+}
 
 void pack_jobs_mfma_dev(torch::Tensor any_bits, torch::Tensor all_bits,
                         torch::Tensor a_pack)
@@ -2463,6 +2925,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::call_guard<py::gil_scoped_release>(),
           "fused host synthetic-batch encoder");
     m.def("pack_jobs_mfma_dev", &pack_jobs_mfma_dev, "device job packing for the MFMA K1");
+    m.def("synthetic_fresh_stamped", &synthetic_fresh_stamped,
+          py::call_guard<py::gil_scoped_release>(),
+          "host batch preparation in one call: synthetic dims + payload step stamp",
+          py::arg("any_bits"), py::arg("all_bits"), py::arg("tenant_lut"),
+          py::arg("topic_lut"), py::arg("risk_lut"), py::arg("req_lut"),
+          py::arg("seed"), py::arg("step"), py::arg("dim_tenant"), py::arg("dim_topic"),
+          py::arg("dim_risk"), py::arg("all_requires"), py::arg("payload"),
+          py::arg("payload_words"), py::arg("threads") = 1, py::arg("isa_cap") = -1);
+    m.def("encoder_isa_level", [] { return cordum_enc::max_isa_level(); },
+          "widest encoder ISA this CPU runs (0 baseline, 1 AVX2, 2 AVX-512DQ)");
+    m.def("tick_prologue", &tick_prologue,
+          "fused tick 1/5: PENDING re-admit + counter reset + first prime + worker keys");
+    m.def("policy_first_match_mfma_bits_into", &policy_first_match_mfma_bits_into,
+          "fused tick 3/5: K1 MFMA with A fragments built from the staged bit words",
+          py::arg("any_bits"), py::arg("all_bits"), py::arg("b_pack"), py::arg("cards"),
+          py::arg("rule_secrets"), py::arg("job_secrets"), py::arg("tile_dims"),
+          py::arg("n_rules"), py::arg("out"), py::arg("job_tiles") = 1);
+    m.def("gate_route", &gate_route,
+          "fused tick 4/5: gate + DENIED/DLQ + spread/exact pick + routable compaction");
+    m.def("tick_finish", &tick_finish,
+          "fused tick 5/5: echo + state chain + load feedback + counter fold");
     m.def("pack_by_dest", &pack_by_dest, "padded per-destination dispatch pack");
     m.def("pack_requeue", &pack_requeue, "redeliver last tick's requeue ring into the send segments");
     m.def("wf_sweep", &wf_sweep, "K3-WF readiness sweep + approval holds + condition/delay commits");

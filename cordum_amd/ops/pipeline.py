@@ -191,6 +191,30 @@ class SyntheticEncoder:
                             self.seed, step,
                             DIM_TENANT, DIM_TOPIC, DIM_RISK, ALL_REQUIRES)
 
+    # encoder threads per call (the call owns them). 1: at 16384 jobs the
+    # blocked loop takes ~62 us on the MI355X host and creating + joining the
+    # helper thread costs more than the half batch it takes over (67 us with
+    # 2, profiles/r51_e2e_legs.txt); the split pays only on larger batches
+    encode_threads = 1
+
+    def fresh_stamped(self, out: JobBatch, step: int, ext, payload: torch.Tensor,
+                      payload_words: int, threads: Optional[int] = None,
+                      isa_cap: int = -1) -> None:
+        """Whole host-side batch preparation in ONE GIL-free native call
+        (ext.synthetic_fresh_stamped): the draws of fresh_fast, bit for bit
+        (same splitmix64 chain, Lemire reductions and cut-offs — fresh_fast
+        is its oracle), plus the per-step stamp of word 0 of every payload
+        row (low 32 bits of the step) that used to be a strided torch op."""
+        DIM_TENANT, DIM_TOPIC, DIM_RISK, ALL_REQUIRES = self._dims
+        ext.synthetic_fresh_stamped(out.any_bits, out.all_bits,
+                                    self.tenant_lut, self.topic_lut,
+                                    self.risk_lut, self.req_lut,
+                                    self.seed, step,
+                                    DIM_TENANT, DIM_TOPIC, DIM_RISK, ALL_REQUIRES,
+                                    payload, payload_words,
+                                    self.encode_threads if threads is None else threads,
+                                    isa_cap)
+
 
 class _RefOps:
     """CPU backend with the HIP extension's call signatures, built on the
@@ -495,6 +519,23 @@ def alloc_batch_staging(B: int, W: int, device=None, pin: bool = False):
     return JobBatch(any_b, all_b, sec, mcp_b, used), buf
 
 
+def alloc_result_block(B: int, device=None, pin: bool = False):
+    """Per-tick results as views of ONE contiguous buffer (the egress twin of
+    alloc_batch_staging): checksums int32[B] | counters int32[4] | decisions
+    int8[B]. Same layout on the device and the pinned host side, so result
+    egress is one D2H copy per step instead of three.
+    Returns (res_sums, counts, out_decision, flat uint8 buffer)."""
+    nbytes = ((4 * B + 16 + B + 7) // 8) * 8
+    if pin:
+        buf = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+    else:
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    sums = buf[0:4 * B].view(torch.int32)
+    counts = buf[4 * B:4 * B + 16].view(torch.int32)
+    dec = buf[4 * B + 16:5 * B + 16].view(torch.int8)
+    return sums, counts, dec, buf
+
+
 class DevicePipeline:
     def __init__(
         self,
@@ -512,8 +553,20 @@ class DevicePipeline:
         use_mfma: Optional[bool] = None,
         mfma_pack_on_device: bool = False,
         pad_cap: Optional[int] = None,
+        unfused_tick: bool = False,
+        k1_job_tiles: int = 2,
     ):
+        # 16-job tiles each K1 wave holds in registers (1 or 2), so one
+        # B-fragment load and one cards gather serve that many MFMAs.
+        # Measured at the bench shape (kernel trace, 4 x 300 ticks each,
+        # spread 0.1 us): 1 -> 31.5 us, 2 -> 27.2 us; 4 was tried and lost
+        # (41.4 us: 215 VGPRs, 2 waves/SIMD);
+        # profiles/r51_k1_register_blocking.txt
+        self._k1_job_tiles = k1_job_tiles
         self._pad_cap_override = pad_cap
+        # True keeps the captured tick on the older one-kernel-per-stage
+        # sequence: the oracle the fused 5-launch tick is tested against
+        self._unfused_tick = unfused_tick
         self._mfma_device_pack = mfma_pack_on_device
         device = torch.device(device)
         self.ext = _RefOps() if backend == "ref" else get_ext(required=True)
@@ -605,12 +658,14 @@ class DevicePipeline:
 
         # result arena: a rank can receive up to world*B jobs in one tick
         self.res_arena = torch.zeros(self.B * self.world * payload_words, dtype=torch.int32, device=device)
-        self.res_sums = torch.zeros(self.B, dtype=torch.int32, device=device)
+        # checksums, decisions and the tick counters share one contiguous block
+        # so the e2e loop reads a step's results back with a single copy
+        (self.res_sums, self._counts, self.out_decision,
+         self._res_block) = alloc_result_block(self.B, device=device)
 
         # fused-tick buffers (single-GPU hipGraph path): fixed-capacity
         # compaction lists + device-resident counts; batch content is copied
         # into staging tensors so one captured graph serves the whole ring
-        self.out_decision = torch.zeros(self.B, dtype=torch.int8, device=device)
         # device-side running totals of the tick counters (read once per
         # timed window by collect_stats — the per-tick D2H read was the
         # tick's only host sync)
@@ -621,7 +676,7 @@ class DevicePipeline:
         self.denied_slots = torch.zeros(self.B, dtype=torch.int32, device=device)
         # one backing tensor for the counters -> one D2H read per tick
         # [0]=denied [1]=allowed [2]=routable [3]=dispatched (padded path)
-        self._counts = torch.zeros(4, dtype=torch.int32, device=device)
+        # (self._counts is a view of the result block above)
         self.denied_count = self._counts[0:1]
         self.allowed_count = self._counts[1:2]
         self.routable_count = self._counts[2:3]
@@ -653,20 +708,27 @@ class DevicePipeline:
             from .policy_mfma import N_DIMS, pack_policy_mfma
 
             self.mfma_policy = pack_policy_mfma(self.compiled).to(device)
-            Jt = (self.B + 15) // 16
-            # packed IN-GRAPH from the staged bit words each tick
-            self.mfma_a_packs = [
-                torch.zeros(Jt, N_DIMS, 64, 16, dtype=torch.int8, device=device)
-                for _ in range(len(self.batches))
-            ]
+            self.mfma_a_packs = []
+            if self._unfused_tick:
+                Jt = (self.B + 15) // 16
+                # packed IN-GRAPH from the staged bit words each tick; the
+                # fused tick's K1 expands the bit words in registers and
+                # needs no pack buffer
+                self.mfma_a_packs = [
+                    torch.zeros(Jt, N_DIMS, 64, 16, dtype=torch.int8, device=device)
+                    for _ in range(len(self.batches))
+                ]
         elif self._use_mfma:
             from .policy_mfma import pack_jobs_mfma, pack_policy_mfma
 
             self.mfma_policy = pack_policy_mfma(self.compiled).to(device)
             self.mfma_a_packs = []
+            # host prepack: only the unfused tick reads it (the fused K1
+            # takes the resident batches' bit words directly)
             for jb_host, jb_dev in zip(
                 [encode_synthetic_jobs(self.compiled, self.B, seed=seed * 1000 + i + rank * 77)
-                 for i in range(len(self.batches))], self.batches
+                 for i in range(len(self.batches) if self._unfused_tick else 0)],
+                self.batches
             ):
                 a_pack, _ = pack_jobs_mfma(jb_host)
                 self.mfma_a_packs.append(a_pack.to(device))
@@ -703,7 +765,70 @@ class DevicePipeline:
         tensors — no host decisions, no staging copies; one captured graph
         per ring slot (the boundary/graph-replay costs in
         MI355X_MICROARCH.md §price-list are what this amortizes for the
-        launch-bound control-plane tick)."""
+        launch-bound control-plane tick).
+
+        Five launches: prologue | K2 exact pick | K1 | gate+route | finish.
+        Ten of the older sequence's launches ran 4.4-8.8 us each over a few
+        thousand threads of work (profiles/r49_e2e_overlap_ktrace_stats.txt),
+        and the main stream's span per step, not the host encode, was what
+        bounded the pipelined ingest step (profiles/r51_ktrace_before.txt)."""
+        if self._unfused_tick:
+            return self._unfused_body(slot)
+        B = self.B
+        ext = self.ext
+        jb = self.batches[slot]
+        full_mask = (1 << self.world) - 1
+        # 1) PENDING re-admit + counters reset + first-match buffer primed to
+        # the atomicMin identity + worker keys from the raw load tensors
+        # (world==1: the global view IS the local view)
+        ext.tick_prologue(self.states, self._counts,
+                          self.first_buf if self._use_mfma else None,
+                          self.w_active_local, self.w_maxp,
+                          self.w_cpu_local, self.w_gpu_local, self.w_keys)
+        # 2) K2 exact pick, constrained jobs only; needs just the keys and the
+        # job masks, so it runs ahead of K1
+        ext.least_loaded_pick_into(self.w_pool, self.w_keys, self.w_labels,
+                                   self.j_poolmask, self.j_labels,
+                                   self.valid_buf, full_mask, self.pick_buf)
+        # 3) K1; the MFMA variant builds its A fragments from the staged bit
+        # words in registers (no pack launch, no pack buffer)
+        if self._use_mfma:
+            ext.policy_first_match_mfma_bits_into(
+                jb.any_bits, jb.all_bits, self.mfma_policy.b_pack,
+                self.mfma_policy.cards, self.mfma_policy.secrets, jb.secrets,
+                self.mfma_policy.tile_dims, self.compiled.n_rules, self.first_buf,
+                self._k1_job_tiles)
+            first = self.first_buf
+        else:
+            first = ext.policy_first_match(
+                self.cpol.any_masks, self.cpol.all_masks, self.cpol.secrets,
+                self.cpol.mcp_masks, self.cpol.mcp_any,
+                jb.any_bits, jb.all_bits, jb.secrets, jb.mcp_bits, jb.mcp_used, 0,
+            )
+        # 4) gate + DENIED/DLQ + K2c spread + routable compaction per job
+        # slot; zeroes the local-load accumulator the prologue has read
+        K = min(int(self.order_buf.shape[0]), 1024)
+        ext.gate_route(first, self.cpol.decisions, self.out_decision,
+                       self.denied_slots, self.denied_count,
+                       self.allowed_slots, self.allowed_count,
+                       self.states, self.deadlines, self.dlq_ring, self.dlq_head,
+                       self.pick_buf, self.order_buf, self.valid_buf,
+                       self.j_poolmask, self.j_labels, full_mask, K,
+                       self.routable_slots, self.routable_widx,
+                       self.routable_count, self.w_active_local)
+        # 5) echo + SCHEDULED..SUCCEEDED chain + load feedback + counter fold
+        ext.tick_finish(self.payloads[slot], self.routable_slots,
+                        self.routable_widx, self.routable_count,
+                        self.res_arena[: B * self.payload_words], self.res_sums,
+                        self.payload_words,
+                        self.states, self.attempts, self.deadlines,
+                        [SCHEDULED, DISPATCHED, RUNNING, SUCCEEDED],
+                        self.w_active_local, self.NWL, self.rank,
+                        self._counts, self.acc_counts, B)
+
+    def _unfused_body(self, slot: int) -> None:
+        """The tick as one kernel per stage (11-12 launches): what the fused
+        sequence replaced, kept as its test oracle."""
         B = self.B
         ext = self.ext
         jb = self.batches[slot]
@@ -919,17 +1044,22 @@ class DevicePipeline:
         lats = [0.0] * steps
         t_enc = [0.0] * steps
         native = hasattr(self.ext, "synthetic_fresh")
+        stamped = hasattr(self.ext, "synthetic_fresh_stamped")
 
         def encode(s: int):
             t_enc[s] = time.perf_counter()
             hb = self._d_hosts[s % nhost]
             enc = self._d_encs[s % nhost]
+            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
+            if stamped:
+                # encode + payload stamp in one GIL-free native call
+                enc.fresh_stamped(hb, s, self.ext, payload, self.payload_words)
+                return
             if native:
                 enc.fresh_fast(hb, s, self.ext)
             else:
                 enc.fresh(hb)
-            self._e2e_payloads[s % len(self._e2e_payloads)].view(
-                self.B, self.payload_words)[:, 0] = s
+            payload.view(self.B, self.payload_words)[:, 0] = s
 
         fut = self._d_pool.submit(encode, 0)
         for s in range(steps):
@@ -1006,12 +1136,12 @@ class DevicePipeline:
             # each buffer owns its generator (single shared generator = race)
             self._e2e_encs = [SyntheticEncoder(self.compiled, seed=101 + 13 * i + self.rank)
                               for i in range(nhost)]
-            self._e2e_out_sums = [torch.zeros(B, dtype=torch.int32).pin_memory()
-                                  for _ in range(nslots)]
-            self._e2e_out_dec = [torch.zeros(B, dtype=torch.int8).pin_memory()
-                                 for _ in range(nslots)]
-            self._e2e_out_counts = [torch.zeros(4, dtype=torch.int32).pin_memory()
-                                    for _ in range(nslots)]
+            # pinned twins of the device result block: one D2H per step
+            outs = [alloc_result_block(B, pin=True) for _ in range(nslots)]
+            self._e2e_out_sums = [o[0] for o in outs]
+            self._e2e_out_counts = [o[1] for o in outs]
+            self._e2e_out_dec = [o[2] for o in outs]
+            self._e2e_out_blocks = [o[3] for o in outs]
             self._e2e_ev = [torch.cuda.Event() for _ in range(nslots)]
             self._e2e_in_ev = [torch.cuda.Event() for _ in range(nslots)]
             self._e2e_copy_stream = torch.cuda.Stream(device=self.device)
@@ -1024,16 +1154,21 @@ class DevicePipeline:
         t_enc = [0.0] * steps
 
         native_enc = hasattr(self.ext, "synthetic_fresh")
+        stamped_enc = hasattr(self.ext, "synthetic_fresh_stamped")
 
         def encode(s: int):
             t_enc[s] = time.perf_counter()
             hb = self._e2e_hosts2[s % nhost]
             enc = self._e2e_encs[s % nhost]
+            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
+            if stamped_enc:
+                # encode + payload stamp in one GIL-free native call
+                enc.fresh_stamped(hb, s, self.ext, payload, W)
+                return
             if native_enc:
                 enc.fresh_fast(hb, s, self.ext)
             else:
                 enc.fresh(hb)
-            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
             payload.view(B, W)[:, 0] = s
 
         def harvest(s_prev: int) -> None:
@@ -1081,9 +1216,8 @@ class DevicePipeline:
                 self._e2e_in_ev[slot].record(self._e2e_copy_stream)
             torch.cuda.current_stream(self.device).wait_event(self._e2e_in_ev[slot])
             self._graphs[slot].replay()
-            self._e2e_out_sums[slot].copy_(self.res_sums, non_blocking=True)
-            self._e2e_out_dec[slot].copy_(self.out_decision, non_blocking=True)
-            self._e2e_out_counts[slot].copy_(self._counts, non_blocking=True)
+            # checksums + counters + decisions: one block, one D2H
+            self._e2e_out_blocks[slot].copy_(self._res_block, non_blocking=True)
             self._e2e_ev[slot].record()
             submit(s + 2)
             if s >= 1:
