@@ -22,6 +22,19 @@
 //  - scoring kernel: score = active + cpu/100 + gpu/100 packed into a
 //    monotonic (score,idx) uint64 key -> deterministic argmin (ties by
 //    lowest worker index, matching the host strategy).
+//
+// Stage bodies: the logic of each tick stage is one __device__
+// __forceinline__ function in the "Tick stage bodies" section below
+// (worker_key, begin_slot, gate_job = gate_decide + gate_append, the K5 rule
+// as apply_one/march_chain, deny_to_dlq, spread_worker/route_pick/
+// route_append, echo_row, wave_histogram_add). The per-stage kernels (eager,
+// padded and staged ticks) call one body each; the fused kernels compose
+// several:
+//   tick_prologue = begin_slot + worker_key
+//   gate_route    = gate_job + deny_to_dlq + route_pick + route_append
+//   tick_finish   = wave_histogram_add + echo_row + march_chain + counter fold
+// The wf_* kernels, K1, the K2 scan, the pack kernels and deadline_scan do
+// not go through them.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -178,12 +191,28 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// K2: least-loaded worker pick
+// Tick stage bodies
 // ---------------------------------------------------------------------------
-// Worker row: pool(int32), active(int32), maxp(int32), cpu(f32), gpu(f32),
-// labels_mask(int64). Job row: pool_mask(int64 over pool vocab), required
-// labels mask(int64), preferred_worker(int32, -1 none).
-// Output per job: packed pick int32 (-1 no_workers, -2 overloaded) .
+// Each stage of the control-plane tick is written ONCE here as a
+// __device__ __forceinline__ body. The __global__ kernels further down (the
+// per-stage ones the eager and padded ticks launch, the *_dyn ones of the
+// staged captured tick, and the three fused ones) hold only the index
+// arithmetic (which thread or wave owns which entry, the bounds, the
+// region-valid test of the padded forms) and call into these, so a change to
+// a stage is a change in one place.
+
+// job states (protocol/states.py JobState) the rules below name
+#define N_STATES 11
+#define STATE_PENDING 1
+#define STATE_SCHEDULED 3
+#define STATE_FIRST_TERMINAL 6   // SUCCEEDED..DENIED are 6..10
+#define STATE_DENIED 10
+#define NO_DEADLINE ((long long)0x7fffffffffffffffLL)
+__constant__ unsigned char d_transition_lut[N_STATES * N_STATES];
+
+// high word of an overloaded worker's key: sorts after every score, before
+// the picker's "no candidate" ~0
+#define OVERLOADED_TAG 0xfffffffeu
 
 __device__ __forceinline__ unsigned long long score_key(float score, int widx) {
     // score >= 0 -> float bits are monotonic; tie-break by lowest index
@@ -191,6 +220,232 @@ __device__ __forceinline__ unsigned long long score_key(float score, int widx) {
     return ((unsigned long long)sb << 32) | (unsigned int)widx;
 }
 
+// Worker key: (score, idx) packed into a monotonic u64; an overloaded worker
+// gets the OVERLOADED_TAG key so the picker can still distinguish "all
+// overloaded" from "no workers". The float expressions stay as written: the
+// key bits depend on how the compiler contracts them.
+__device__ __forceinline__ unsigned long long worker_key(
+    int i, int active, int maxp, float cpu, float gpu)
+{
+    bool over = false;
+    if (maxp > 0 && (float)active / (float)maxp >= 0.9f) over = true;
+    if (cpu >= 90.f || gpu >= 90.f) over = true;
+    if (over) return ((unsigned long long)OVERLOADED_TAG << 32) | (unsigned int)i;
+    const float score = (float)active + cpu * 0.01f + gpu * 0.01f;
+    return score_key(score, i);
+}
+
+// Tick prologue for grid thread i: every ring slot is re-admitted as PENDING
+// (CREATED -> PENDING is the only LUT edge exercised by the old zero_() +
+// apply_transitions pair, so write it directly), `first` (if given) is
+// primed to the atomicMin identity, and the counter words reset.
+__device__ __forceinline__ void begin_slot(
+    int i, unsigned char* states, int B, int* counts, int ncounts, int* first)
+{
+    if (i < B) {
+        states[i] = STATE_PENDING;
+        if (first != nullptr) first[i] = INT_MAX;
+    }
+    if (i < ncounts) counts[i] = 0;
+}
+
+// wave-aggregated compaction append: one atomicAdd per wave instead of one
+// per lane (a single counter word saturates at ~88 atomics/us on this chip —
+// MI355X_MICROARCH.md price-list row "dequeue")
+__device__ __forceinline__ int wave_append_slot(bool pred, int* counter, int lane) {
+    const unsigned long long mask = __ballot(pred);
+    const int nactive = __popcll(mask);
+    int base = 0;
+    const int leader = __ffsll((long long)mask) - 1;
+    if (pred && lane == leader) base = atomicAdd(counter, nactive);
+    base = __shfl(base, leader, WAVE);
+    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+    return pred ? base + rank : -1;
+}
+
+// Gate decision of job j: the first-matched rule's decision, default allow.
+// No-match is -1 (host-masked) OR anything out of range: the raw INT_MAX
+// atomicMin identity when the producer skipped the mask pass (_into variants)
+__device__ __forceinline__ signed char gate_decide(
+    const int* first, const signed char* decisions, int R, int j)
+{
+    const int r = first[j];
+    return (r >= 0 && r < R) ? decisions[r] : (signed char)1;
+}
+
+// Allowed/denied split of a live job into the two compacted lists (whole
+// wave calls this; dead lanes pass live=false). Returns "allowed".
+__device__ __forceinline__ bool gate_append(
+    bool live, signed char d, int j, int lane,
+    int* allowed_slots, int* allowed_count, int* denied_slots, int* denied_count)
+{
+    const bool allowed = live && (d == 1 || d == 5);
+    const int apos = wave_append_slot(allowed, allowed_count, lane);
+    if (apos >= 0) allowed_slots[apos] = j;
+    const bool denied = live && !allowed;
+    const int dpos = wave_append_slot(denied, denied_count, lane);
+    if (dpos >= 0) denied_slots[dpos] = j;
+    return allowed;
+}
+
+// The gate for grid thread j of J jobs: decide, record the decision, split.
+// Returns "allowed".
+__device__ __forceinline__ bool gate_job(
+    int j, int J, int lane, const int* first, const signed char* decisions, int R,
+    signed char* out_decision,
+    int* allowed_slots, int* allowed_count, int* denied_slots, int* denied_count)
+{
+    const bool live = j < J;
+    signed char d = 0;
+    if (live) {
+        d = gate_decide(first, decisions, R, j);
+        out_decision[j] = d;
+    }
+    return gate_append(live, d, j, lane, allowed_slots, allowed_count,
+                       denied_slots, denied_count);
+}
+
+// K5 rule, one hop, on a state held in a register (job_store.go:70-82):
+// legal per the LUT or nothing happens; attempts increment on entering
+// SCHEDULED. Advances `cur` and returns true when the hop is legal.
+__device__ __forceinline__ bool transition_hop(
+    unsigned char& cur, unsigned char to, int* attempts, int slot)
+{
+    if (!d_transition_lut[cur * N_STATES + to]) return false;
+    if (to == STATE_SCHEDULED && cur != STATE_SCHEDULED) attempts[slot] += 1;
+    cur = to;
+    return true;
+}
+
+// ... and the write-back: terminal states clear the deadline
+__device__ __forceinline__ void commit_state(
+    unsigned char* states, long long* deadlines, int slot, unsigned char cur)
+{
+    states[slot] = cur;
+    if (cur >= STATE_FIRST_TERMINAL) deadlines[slot] = NO_DEADLINE;
+}
+
+// One K5 transition of `slot`; an illegal one writes nothing. `attempts` is
+// only touched when `to` is SCHEDULED.
+__device__ __forceinline__ bool apply_one(
+    unsigned char* states, int* attempts, long long* deadlines, int slot, unsigned char to)
+{
+    unsigned char cur = states[slot];
+    if (!transition_hop(cur, to, attempts, slot)) return false;
+    commit_state(states, deadlines, slot, cur);
+    return true;
+}
+
+// Chained K5: march `slot` through up to 4 states (-1 = unused), LUT-checked
+// hop by hop, stopping at the first illegal one; the state reached is
+// written back once.
+__device__ __forceinline__ void march_chain(
+    unsigned char* states, int* attempts, long long* deadlines, int slot,
+    const int (&chain)[4])
+{
+    unsigned char cur = states[slot];
+    #pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (chain[c] < 0) break;
+        if (!transition_hop(cur, (unsigned char)chain[c], attempts, slot)) break;
+    }
+    commit_state(states, deadlines, slot, cur);
+}
+
+// DENIED transition of a denied job + DLQ ring append (K7: dlq_store.go's
+// capped index as an HBM ring with an atomic head). Whole wave calls this.
+__device__ __forceinline__ void deny_to_dlq(
+    bool denied, int j, int lane, unsigned char* states, long long* deadlines,
+    int* dlq_ring, int* dlq_head, int ring_size)
+{
+    const bool dlq = denied && apply_one(states, nullptr, deadlines, j, STATE_DENIED);
+    const int rpos = wave_append_slot(dlq, dlq_head, lane);
+    if (rpos >= 0) dlq_ring[rpos % ring_size] = j;
+}
+
+// K2c: batch spreading — unconstrained jobs round-robin over the K least
+// loaded workers. A frozen-snapshot argmin sends a whole homogeneous batch
+// to ONE worker (the reference has the same pathology between heartbeats:
+// its scheduler replica piles onto the lowest scorer until the next 10 s
+// heartbeat); queue-group fan-in is the intended behavior, and spreading a
+// batch across the least-loaded set IS that behavior for a batched tick.
+// Constrained jobs (labels / narrowed pool mask) keep their exact scan pick.
+// Returns job j's spread worker, or -1 when j keeps its exact pick (it is
+// constrained, or every worker is overloaded).
+__device__ __forceinline__ int spread_worker(
+    int j, const int* order, const int* valid_count,
+    const long long* j_poolmask, const long long* j_labels, long long full_mask, int K)
+{
+    if (j_labels[j] != 0 || j_poolmask[j] != full_mask) return -1;
+    const int V = min(*valid_count, K);
+    return (V > 0) ? order[j % V] : -1;
+}
+
+// Route of job j: the spread if it takes one, else the exact pick (<0 = none)
+__device__ __forceinline__ int route_pick(
+    int j, const int* pick, const int* order, const int* valid_count,
+    const long long* j_poolmask, const long long* j_labels, long long full_mask, int K)
+{
+    const int s = spread_worker(j, order, valid_count, j_poolmask, j_labels, full_mask, K);
+    return s >= 0 ? s : pick[j];
+}
+
+// Routable compaction: jobs with a worker (w >= 0) go to the routable list.
+// Whole wave calls this; lanes without a job pass w < 0.
+__device__ __forceinline__ void route_append(
+    int j, int w, int lane, int* routable_slots, int* routable_widx, int* routable_count)
+{
+    const int pos = wave_append_slot(w >= 0, routable_count, lane);
+    if (pos >= 0) {
+        routable_slots[pos] = j;
+        routable_widx[pos] = w;
+    }
+}
+
+// Echo worker, one wave per job: lanes stream the payload row, echo it into
+// the result row (memory-bound, like the reference's echo worker copying
+// ctx -> res through Redis) and wave-reduce a checksum, returned in lane 0.
+__device__ __forceinline__ unsigned int echo_row(
+    const unsigned int* src, unsigned int* dst, int stride, int lane)
+{
+    unsigned int acc = 0;
+    for (int k = lane; k < stride; k += WAVE) {
+        const unsigned int v = src[k];
+        dst[k] = v;
+        acc += v;
+    }
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        acc += __shfl_down(acc, off, WAVE);
+    return acc;
+}
+
+// Load histogram, wave match-any aggregation: a frozen-snapshot least-loaded
+// pick is highly concentrated (often ONE worker for a whole homogeneous
+// batch), so per-lane atomics serialize on a single word (~88 atomics/us).
+// Group lanes by equal bin and issue one atomicAdd per distinct value.
+// Whole wave calls this; lanes without an entry pass live=false.
+__device__ __forceinline__ void wave_histogram_add(bool live, int bin, int* hist, int lane)
+{
+    unsigned long long pending = __ballot(live);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int leader_bin = __shfl(bin, leader, WAVE);
+        const unsigned long long same = __ballot(live && bin == leader_bin);
+        if (lane == leader) atomicAdd(&hist[leader_bin], __popcll(same));
+        pending &= ~same;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K2: least-loaded worker pick
+// ---------------------------------------------------------------------------
+// Worker row: pool(int32), active(int32), maxp(int32), cpu(f32), gpu(f32),
+// labels_mask(int64). Job row: pool_mask(int64 over pool vocab), required
+// labels mask(int64), preferred_worker(int32, -1 none).
+// Output per job: packed pick int32 (-1 no_workers, -2 overloaded) .
+
+// per-worker tick-invariant precompute of the keys
 __global__ __launch_bounds__(BLOCK) void worker_precompute_kernel(
     const int* __restrict__ w_pool,        // [W]
     const int* __restrict__ w_active,      // [W]
@@ -200,25 +455,10 @@ __global__ __launch_bounds__(BLOCK) void worker_precompute_kernel(
     unsigned long long* __restrict__ w_key, // [W] out: (score,idx) or flags
     int NW)
 {
-    // per-worker tick-invariant precompute: pack (score, idx) into a
-    // monotonic u64 key; overloaded workers get OVERLOADED_KEY so the picker
-    // can still distinguish "all overloaded" from "no workers".
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= NW) return;
-    const int active = w_active[i], maxp = w_maxp[i];
-    const float cpu = w_cpu[i], gpu = w_gpu[i];
-    bool over = false;
-    if (maxp > 0 && (float)active / (float)maxp >= 0.9f) over = true;
-    if (cpu >= 90.f || gpu >= 90.f) over = true;
-    if (over) {
-        w_key[i] = 0xfffffffe00000000ull | (unsigned int)i;  // OVERLOADED
-    } else {
-        const float score = (float)active + cpu * 0.01f + gpu * 0.01f;
-        w_key[i] = score_key(score, i);
-    }
+    w_key[i] = worker_key(i, w_active[i], w_maxp[i], w_cpu[i], w_gpu[i]);
 }
-
-#define OVERLOADED_TAG 0xfffffffeu
 
 __global__ __launch_bounds__(BLOCK) void least_loaded_pick_kernel(
     const int* __restrict__ w_pool,         // [W]
@@ -313,13 +553,7 @@ __global__ __launch_bounds__(BLOCK) void least_loaded_pick_kernel(
     }
 }
 
-// K2c: batch spreading — unconstrained jobs round-robin over the K least
-// loaded workers. A frozen-snapshot argmin sends a whole homogeneous batch
-// to ONE worker (the reference has the same pathology between heartbeats:
-// its scheduler replica piles onto the lowest scorer until the next 10 s
-// heartbeat); queue-group fan-in is the intended behavior, and spreading a
-// batch across the least-loaded set IS that behavior for a batched tick.
-// Constrained jobs (labels / narrowed pool mask) keep their exact scan pick.
+// K2c spread applied in place over the exact picks (spread_worker)
 __global__ __launch_bounds__(BLOCK) void spread_pick_kernel(
     const int* __restrict__ order,        // [NW] worker idx sorted by key asc
     const int* __restrict__ valid_count,  // [1] non-overloaded workers
@@ -331,17 +565,13 @@ __global__ __launch_bounds__(BLOCK) void spread_pick_kernel(
 {
     const int j = blockIdx.x * BLOCK + threadIdx.x;
     if (j >= NJ) return;
-    if (j_labels[j] != 0 || j_poolmask[j] != full_mask) return;  // constrained
-    const int V = min(*valid_count, K);
-    if (V > 0) pick[j] = order[j % V];
+    const int s = spread_worker(j, order, valid_count, j_poolmask, j_labels, full_mask, K);
+    if (s >= 0) pick[j] = s;
 }
 
 // ---------------------------------------------------------------------------
-// K5: batched state transitions with legality LUT (job_store.go:70-82)
+// K5: batched state transitions with legality LUT (apply_one)
 // ---------------------------------------------------------------------------
-#define N_STATES 11
-__constant__ unsigned char d_transition_lut[N_STATES * N_STATES];
-
 __global__ __launch_bounds__(BLOCK) void apply_transitions_kernel(
     unsigned char* __restrict__ states,     // [N] job table states
     int* __restrict__ attempts,             // [N]
@@ -353,31 +583,7 @@ __global__ __launch_bounds__(BLOCK) void apply_transitions_kernel(
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= B) return;
-    const int slot = slots[i];
-    const unsigned char to = to_states[i];
-    const unsigned char from = states[slot];
-    const unsigned char legal = d_transition_lut[from * N_STATES + to];
-    ok_out[i] = legal;
-    if (!legal) return;
-    states[slot] = to;
-    // attempts increment on entering SCHEDULED (JobState.SCHEDULED == 3)
-    if (to == 3 && from != 3) attempts[slot] += 1;
-    // terminal states clear the deadline (SUCCEEDED..DENIED are 6..10)
-    if (to >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
-}
-
-// wave-aggregated compaction append: one atomicAdd per wave instead of one
-// per lane (a single counter word saturates at ~88 atomics/us on this chip —
-// MI355X_MICROARCH.md price-list row "dequeue")
-__device__ __forceinline__ int wave_append_slot(bool pred, int* counter, int lane) {
-    const unsigned long long mask = __ballot(pred);
-    const int nactive = __popcll(mask);
-    int base = 0;
-    const int leader = __ffsll((long long)mask) - 1;
-    if (pred && lane == leader) base = atomicAdd(counter, nactive);
-    base = __shfl(base, leader, WAVE);
-    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-    return pred ? base + rank : -1;
+    ok_out[i] = apply_one(states, attempts, deadlines, slots[i], to_states[i]);
 }
 
 // K7: DLQ ring append — denied/failed slots into a capped device ring
@@ -892,23 +1098,12 @@ __global__ __launch_bounds__(BLOCK) void echo_worker_kernel(
     unsigned int* __restrict__ res_sum,          // [B]
     int B, int stride)
 {
-    // one wave per job: lanes stream the payload, wave-reduce a checksum,
-    // and echo the payload into the result arena (memory-bound, like the
-    // reference's echo worker copying ctx -> res through Redis).
+    // one wave per job, rows in batch order (echo_row)
     const int wave_id = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
     const int lane = threadIdx.x % WAVE;
     if (wave_id >= B) return;
     const size_t basep = (size_t)wave_id * stride;
-    unsigned int acc = 0;
-    for (int k = lane; k < stride; k += WAVE) {
-        const unsigned int v = ctx_arena[basep + k];
-        res_arena[basep + k] = v;
-        acc += v;
-    }
-    // wave reduction
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_down(acc, off, WAVE);
+    const unsigned int acc = echo_row(ctx_arena + basep, res_arena + basep, stride, lane);
     if (lane == 0) res_sum[wave_id] = acc;
 }
 
@@ -927,15 +1122,7 @@ __global__ __launch_bounds__(BLOCK) void echo_worker_indexed_kernel(
     if (w >= B) return;
     const int slot = slots[w];
     const size_t basep = (size_t)slot * stride;
-    unsigned int acc = 0;
-    for (int k = lane; k < stride; k += WAVE) {
-        const unsigned int v = ctx_arena[basep + k];
-        res_arena[basep + k] = v;
-        acc += v;
-    }
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_down(acc, off, WAVE);
+    const unsigned int acc = echo_row(ctx_arena + basep, res_arena + basep, stride, lane);
     if (lane == 0) res_sum[slot] = acc;
 }
 
@@ -1156,23 +1343,12 @@ __global__ __launch_bounds__(BLOCK) void policy_gate_kernel(
     int* __restrict__ denied_count,           // [1]
     int* __restrict__ allowed_slots,          // [J] compacted
     int* __restrict__ allowed_count,          // [1]
-    int J)
+    int J, int R)
 {
     const int j = blockIdx.x * BLOCK + threadIdx.x;
     const int lane = threadIdx.x % WAVE;
-    const bool live = j < J;
-    signed char d = 0;
-    if (live) {
-        const int r = first[j];
-        d = (r >= 0) ? decisions[r] : (signed char)1;  // default allow
-        out_decision[j] = d;
-    }
-    const bool allowed = live && (d == 1 || d == 5);
-    const int apos = wave_append_slot(allowed, allowed_count, lane);
-    if (apos >= 0) allowed_slots[apos] = j;
-    const bool denied = live && !allowed;
-    const int dpos = wave_append_slot(denied, denied_count, lane);
-    if (dpos >= 0) denied_slots[dpos] = j;
+    gate_job(j, J, lane, first, decisions, R, out_decision,
+             allowed_slots, allowed_count, denied_slots, denied_count);
 }
 
 // gate + DENIED transition + DLQ ring in ONE launch: the profile showed the
@@ -1197,60 +1373,18 @@ __global__ __launch_bounds__(BLOCK) void policy_gate_full_kernel(
 {
     const int j = blockIdx.x * BLOCK + threadIdx.x;
     const int lane = threadIdx.x % WAVE;
-    const bool live = j < J;
-    signed char d = 0;
-    if (live) {
-        const int r = first[j];
-        // no-match is -1 (host-masked) OR the raw INT_MAX atomicMin identity
-        // when the producer skipped the mask pass (_into variants)
-        d = (r >= 0 && r < R) ? decisions[r] : (signed char)1;  // default allow
-        out_decision[j] = d;
-    }
-    const bool allowed = live && (d == 1 || d == 5);
-    const int apos = wave_append_slot(allowed, allowed_count, lane);
-    if (apos >= 0) allowed_slots[apos] = j;
-    const bool denied = live && !allowed;
-    const int dpos = wave_append_slot(denied, denied_count, lane);
-    if (dpos >= 0) denied_slots[dpos] = j;
-    // DENIED transition (LUT-checked) + terminal deadline clear, fused
-    bool dlq = false;
-    if (denied) {
-        const unsigned char from = states[j];
-        if (d_transition_lut[from * N_STATES + 10]) {  // -> DENIED
-            states[j] = 10;
-            deadlines[j] = (long long)0x7fffffffffffffffLL;
-            dlq = true;
-        }
-    }
-    const int rpos = wave_append_slot(dlq, dlq_head, lane);
-    if (rpos >= 0) dlq_ring[rpos % ring_size] = j;
+    const bool allowed = gate_job(j, J, lane, first, decisions, R, out_decision,
+                                  allowed_slots, allowed_count, denied_slots, denied_count);
+    deny_to_dlq(j < J && !allowed, j, lane, states, deadlines, dlq_ring, dlq_head, ring_size);
 }
 
-// one-launch per-tick reset: states + the small counter words (replaces two
-// torch zero_() elementwise launches inside the captured tick)
-__global__ __launch_bounds__(BLOCK) void tick_reset_kernel(
-    unsigned char* __restrict__ states, int B,
-    int* __restrict__ counts, int ncounts)
-{
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < B) states[i] = 0;
-    if (i < ncounts) counts[i] = 0;
-}
-
-// tick prologue in one launch: every ring slot is re-admitted as PENDING
-// (CREATED -> PENDING is the only LUT edge exercised by the old zero_() +
-// apply_transitions pair, so write it directly) and the counter words reset
+// tick prologue in one launch (begin_slot)
 __global__ __launch_bounds__(BLOCK) void begin_tick_kernel(
     unsigned char* __restrict__ states, int B,
     int* __restrict__ counts, int ncounts,
     int* __restrict__ first)               // [B] primed for atomicMin, or null
 {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < B) {
-        states[i] = 1;  // PENDING
-        if (first != nullptr) first[i] = INT_MAX;
-    }
-    if (i < ncounts) counts[i] = 0;
+    begin_slot(blockIdx.x * BLOCK + threadIdx.x, states, B, counts, ncounts, first);
 }
 
 // end-of-tick stats fold: the per-tick D2H counts read was the tick's only
@@ -1286,18 +1420,9 @@ __global__ __launch_bounds__(BLOCK) void compact_routable_spread_kernel(
     int j = 0, w = -1;
     if (live) {
         j = allowed_slots[i];
-        if (j_labels[j] == 0 && j_poolmask[j] == full_mask) {
-            const int V = min(*valid_count, K);
-            w = (V > 0) ? order[j % V] : pick[j];
-        } else {
-            w = pick[j];  // constrained: keep the exact scan pick
-        }
+        w = route_pick(j, pick, order, valid_count, j_poolmask, j_labels, full_mask, K);
     }
-    const int pos = wave_append_slot(live && w >= 0, routable_count, lane);
-    if (pos >= 0) {
-        routable_slots[pos] = j;
-        routable_widx[pos] = w;
-    }
+    route_append(j, w, lane, routable_slots, routable_widx, routable_count);
 }
 
 // routable compaction: allowed jobs with a worker pick
@@ -1317,11 +1442,7 @@ __global__ __launch_bounds__(BLOCK) void compact_routable_kernel(
         j = allowed_slots[i];
         w = pick[j];
     }
-    const int pos = wave_append_slot(live && w >= 0, routable_count, lane);
-    if (pos >= 0) {
-        routable_slots[pos] = j;
-        routable_widx[pos] = w;
-    }
+    route_append(j, w, lane, routable_slots, routable_widx, routable_count);
 }
 
 // K5 with device-resident count + uniform target state
@@ -1335,18 +1456,13 @@ __global__ __launch_bounds__(BLOCK) void apply_transitions_dyn_kernel(
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= *count) return;
-    const int slot = slots[i];
-    const unsigned char from = states[slot];
-    if (!d_transition_lut[from * N_STATES + to]) return;
-    states[slot] = to;
-    if (to == 3 && from != 3) attempts[slot] += 1;
-    if (to >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
+    apply_one(states, attempts, deadlines, slots[i], to);
 }
 
-// chained K5: march each routed slot through up to 4 states in ONE launch
-// (SCHEDULED -> DISPATCHED -> RUNNING -> SUCCEEDED after the echo worker; the
-// intermediate states are unobservable inside a captured graph, so four
-// launches over the identical slot set were pure launch tax — see
+// chained K5 (march_chain): each routed slot through up to 4 states in ONE
+// launch (SCHEDULED -> DISPATCHED -> RUNNING -> SUCCEEDED after the echo
+// worker; the intermediate states are unobservable inside a captured graph,
+// so four launches over the identical slot set were pure launch tax — see
 // profiles/r14_bench_ktrace_stats.txt: apply_transitions_dyn 5x/tick, 13.6%).
 // Also zeroes an extra int region (the per-tick local-load accumulator) so
 // the load_feedback pass starts clean without its own zero_() launch.
@@ -1362,19 +1478,8 @@ __global__ __launch_bounds__(BLOCK) void apply_transitions_chain_dyn_kernel(
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < n_extra) extra_zero[i] = 0;
     if (i >= *count) return;
-    const int slot = slots[i];
-    unsigned char from = states[slot];
     const int chain[4] = {to0, to1, to2, to3};
-    #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (chain[c] < 0) break;
-        const unsigned char to = (unsigned char)chain[c];
-        if (!d_transition_lut[from * N_STATES + to]) break;
-        if (to == 3 && from != 3) attempts[slot] += 1;
-        from = to;
-    }
-    states[slot] = from;
-    if (from >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
+    march_chain(states, attempts, deadlines, slots[i], chain);
 }
 
 __global__ __launch_bounds__(BLOCK) void echo_worker_indexed_dyn_kernel(
@@ -1390,29 +1495,18 @@ __global__ __launch_bounds__(BLOCK) void echo_worker_indexed_dyn_kernel(
     if (w >= *count) return;
     const int slot = slots[w];
     const size_t basep = (size_t)slot * stride;
-    unsigned int acc = 0;
-    for (int k = lane; k < stride; k += WAVE) {
-        const unsigned int v = ctx_arena[basep + k];
-        res_arena[basep + k] = v;
-        acc += v;
-    }
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_down(acc, off, WAVE);
+    const unsigned int acc = echo_row(ctx_arena + basep, res_arena + basep, stride, lane);
     if (lane == 0) res_sum[slot] = acc;
 }
 
-// per-worker active-count histogram from the routable list
+// per-worker active-count histogram from the routable list: entries whose
+// worker lives on this rank (wave_histogram_add)
 __global__ __launch_bounds__(BLOCK) void load_feedback_kernel(
     const int* __restrict__ routable_widx,
     const int* __restrict__ count,
     int* __restrict__ w_active_local,         // [NWL] pre-zeroed
     int nwl, int my_rank)
 {
-    // wave match-any aggregation: a frozen-snapshot least-loaded pick is
-    // highly concentrated (often ONE worker for a whole homogeneous batch),
-    // so per-lane atomics serialize on a single word (~88 atomics/us).
-    // Group lanes by equal widx and issue one atomicAdd per distinct value.
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     const int lane = threadIdx.x % WAVE;
     bool live = i < *count;
@@ -1422,22 +1516,19 @@ __global__ __launch_bounds__(BLOCK) void load_feedback_kernel(
         if (w / nwl == my_rank) bin = w % nwl;
         else live = false;
     }
-    unsigned long long pending = __ballot(live);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int leader_bin = __shfl(bin, leader, WAVE);
-        const unsigned long long same = __ballot(live && bin == leader_bin);
-        if (lane == leader) atomicAdd(&w_active_local[leader_bin], __popcll(same));
-        pending &= ~same;
-    }
+    wave_histogram_add(live, bin, w_active_local, lane);
 }
 
 // ---------------------------------------------------------------------------
 // Fused single-GPU tick: prologue | K2 pick | K1 | gate+route | finish.
-// The kernels above stay as they are (the eager and padded ticks call them,
-// and tests/test_gpu_tick_fusion.py holds the fused ones to them). Ten of
-// the old tick's twelve launches ran 4.4-8.8 us each over a few thousand
-// threads of work (profiles/r49_e2e_overlap_ktrace_stats.txt): launch tax.
+// Ten of the old tick's twelve launches ran 4.4-8.8 us each over a few
+// thousand threads of work (profiles/r49_e2e_overlap_ktrace_stats.txt):
+// launch tax. The three kernels below call the same stage bodies as the
+// per-stage kernels above (which the eager, padded and staged ticks still
+// launch), several per launch. Sharing the bodies means the staged tick on
+// the GPU no longer checks them; tests/test_gpu_tick_fusion.py also holds
+// the fused tick to the staged tick on the CPU reference backend, which
+// shares no code with this file.
 // ---------------------------------------------------------------------------
 
 // begin_tick_first + worker_precompute_into in one launch. w_key is written
@@ -1453,24 +1544,8 @@ __global__ __launch_bounds__(BLOCK) void tick_prologue_kernel(
     unsigned long long* __restrict__ w_key, int NW)
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < B) {
-        states[i] = 1;  // PENDING
-        if (first != nullptr) first[i] = INT_MAX;
-    }
-    if (i < ncounts) counts[i] = 0;
-    if (i < NW) {
-        const int active = w_active[i], maxp = w_maxp[i];
-        const float cpu = w_cpu[i], gpu = w_gpu[i];
-        bool over = false;
-        if (maxp > 0 && (float)active / (float)maxp >= 0.9f) over = true;
-        if (cpu >= 90.f || gpu >= 90.f) over = true;
-        if (over) {
-            w_key[i] = 0xfffffffe00000000ull | (unsigned int)i;  // OVERLOADED
-        } else {
-            const float score = (float)active + cpu * 0.01f + gpu * 0.01f;
-            w_key[i] = score_key(score, i);
-        }
-    }
+    begin_slot(i, states, B, counts, ncounts, first);
+    if (i < NW) w_key[i] = worker_key(i, w_active[i], w_maxp[i], w_cpu[i], w_gpu[i]);
 }
 
 // policy_gate_full + compact_routable_spread in one launch, one thread per
@@ -1502,45 +1577,13 @@ __global__ __launch_bounds__(BLOCK) void gate_route_kernel(
     const int j = blockIdx.x * BLOCK + threadIdx.x;
     const int lane = threadIdx.x % WAVE;
     if (j < n_extra) extra_zero[j] = 0;
-    const bool live = j < J;
-    signed char d = 0;
-    if (live) {
-        const int r = first[j];
-        d = (r >= 0 && r < R) ? decisions[r] : (signed char)1;  // default allow
-        out_decision[j] = d;
-    }
-    const bool allowed = live && (d == 1 || d == 5);
-    const int apos = wave_append_slot(allowed, allowed_count, lane);
-    if (apos >= 0) allowed_slots[apos] = j;
-    const bool denied = live && !allowed;
-    const int dpos = wave_append_slot(denied, denied_count, lane);
-    if (dpos >= 0) denied_slots[dpos] = j;
-    bool dlq = false;
-    if (denied) {
-        const unsigned char from = states[j];
-        if (d_transition_lut[from * N_STATES + 10]) {  // -> DENIED
-            states[j] = 10;
-            deadlines[j] = (long long)0x7fffffffffffffffLL;
-            dlq = true;
-        }
-    }
-    const int rpos = wave_append_slot(dlq, dlq_head, lane);
-    if (rpos >= 0) dlq_ring[rpos % ring_size] = j;
-    // route: K2c spread for unconstrained jobs, exact scan pick otherwise
+    const bool allowed = gate_job(j, J, lane, first, decisions, R, out_decision,
+                                  allowed_slots, allowed_count, denied_slots, denied_count);
+    deny_to_dlq(j < J && !allowed, j, lane, states, deadlines, dlq_ring, dlq_head, ring_size);
     int w = -1;
-    if (allowed) {
-        if (j_labels[j] == 0 && j_poolmask[j] == full_mask) {
-            const int V = min(*valid_count, K);
-            w = (V > 0) ? order[j % V] : pick[j];
-        } else {
-            w = pick[j];
-        }
-    }
-    const int pos = wave_append_slot(w >= 0, routable_count, lane);
-    if (pos >= 0) {
-        routable_slots[pos] = j;
-        routable_widx[pos] = w;
-    }
+    if (allowed)
+        w = route_pick(j, pick, order, valid_count, j_poolmask, j_labels, full_mask, K);
+    route_append(j, w, lane, routable_slots, routable_widx, routable_count);
 }
 
 // echo_execute_indexed_dyn + apply_transitions_chain_dyn + load_feedback +
@@ -1581,41 +1624,16 @@ __global__ __launch_bounds__(BLOCK) void tick_finish_kernel(
         if (wk / nwl == my_rank) bin = wk % nwl;
         else live = false;
     }
-    unsigned long long pending = __ballot(live);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int leader_bin = __shfl(bin, leader, WAVE);
-        const unsigned long long same = __ballot(live && bin == leader_bin);
-        if (lane == leader) atomicAdd(&w_active_local[leader_bin], __popcll(same));
-        pending &= ~same;
-    }
+    wave_histogram_add(live, bin, w_active_local, lane);
 
     if (w >= n) return;  // wave-uniform
     const int slot = slots[w];
     const size_t basep = (size_t)slot * stride;
-    unsigned int sum = 0;
-    for (int k = lane; k < stride; k += WAVE) {
-        const unsigned int v = ctx_arena[basep + k];
-        res_arena[basep + k] = v;
-        sum += v;
-    }
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        sum += __shfl_down(sum, off, WAVE);
+    const unsigned int sum = echo_row(ctx_arena + basep, res_arena + basep, stride, lane);
     if (lane == 0) {
         res_sum[slot] = sum;
-        unsigned char from = states[slot];
         const int chain[4] = {to0, to1, to2, to3};
-        #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (chain[c] < 0) break;
-            const unsigned char to = (unsigned char)chain[c];
-            if (!d_transition_lut[from * N_STATES + to]) break;
-            if (to == 3 && from != 3) attempts[slot] += 1;
-            from = to;
-        }
-        states[slot] = from;
-        if (from >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
+        march_chain(states, attempts, deadlines, slot, chain);
     }
 }
 
@@ -1806,15 +1824,7 @@ __global__ __launch_bounds__(BLOCK) void echo_padded_kernel(
     const int region = w / cap, e = w % cap;
     if (e >= recv_cnt[region]) return;
     const size_t basep = (size_t)w * stride;
-    unsigned int acc = 0;
-    for (int k = lane; k < stride; k += WAVE) {
-        const unsigned int v = recv_payload[basep + k];
-        res_arena[basep + k] = v;
-        acc += v;
-    }
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_down(acc, off, WAVE);
+    const unsigned int acc = echo_row(recv_payload + basep, res_arena + basep, stride, lane);
     if (lane == 0) res_sums[w] = acc;
 }
 
@@ -1832,11 +1842,7 @@ __global__ __launch_bounds__(BLOCK) void apply_transitions_padded_kernel(
     if ((i % cap) >= cnt[i / cap]) return;
     const int slot = slots_pad[i];
     if (slot < 0) return;  // redelivered entry: its batch slot was recycled
-    const unsigned char from = states[slot];
-    if (!d_transition_lut[from * N_STATES + to]) return;
-    states[slot] = to;
-    if (to == 3 && from != 3) attempts[slot] += 1;
-    if (to >= 6) deadlines[slot] = (long long)0x7fffffffffffffffLL;
+    apply_one(states, attempts, deadlines, slot, to);
 }
 
 // region-valid per-worker load histogram from padded recv widx
@@ -1848,17 +1854,9 @@ __global__ __launch_bounds__(BLOCK) void load_feedback_padded_kernel(
 {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     const int lane = threadIdx.x % WAVE;
-    bool live = (i < world * cap) && ((i % cap) < recv_cnt[i / cap]);
-    int bin = live ? recv_widx[i] : -1;
-    unsigned long long pending = __ballot(live);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int leader_bin = __shfl(bin, leader, WAVE);
-        const unsigned long long same = __ballot(live && bin == leader_bin);
-        if (lane == leader) atomicAdd(&w_active_local[leader_bin], __popcll(same));
-        pending &= ~same;
-        live = live && bin != leader_bin;
-    }
+    const bool live = (i < world * cap) && ((i % cap) < recv_cnt[i / cap]);
+    const int bin = live ? recv_widx[i] : -1;
+    wave_histogram_add(live, bin, w_active_local, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -1898,6 +1896,7 @@ __global__ __launch_bounds__(BLOCK) void pack_jobs_mfma_kernel(
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <array>
 
 #include "synthetic_encode.h"
 
@@ -2179,7 +2178,8 @@ void policy_gate(torch::Tensor first, torch::Tensor decisions, torch::Tensor out
         first.data_ptr<int>(), (const signed char*)decisions.data_ptr<int8_t>(),
         (signed char*)out_decision.data_ptr<int8_t>(),
         denied_slots.data_ptr<int>(), denied_count.data_ptr<int>(),
-        allowed_slots.data_ptr<int>(), allowed_count.data_ptr<int>(), J);
+        allowed_slots.data_ptr<int>(), allowed_count.data_ptr<int>(),
+        J, (int)decisions.size(0));
 }
 
 void compact_routable(torch::Tensor allowed_slots, torch::Tensor allowed_count,
@@ -2211,35 +2211,27 @@ void policy_gate_full(torch::Tensor first, torch::Tensor decisions, torch::Tenso
         dlq_ring.data_ptr<int>(), dlq_head.data_ptr<int>(),
         (int)dlq_ring.size(0), J, (int)decisions.size(0));
 }
-void tick_reset(torch::Tensor states, torch::Tensor counts)
-{
-    const int B = (int)states.size(0);
-    const int n = (int)counts.size(0);
-    const int blocks = (std::max(B, n) + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(tick_reset_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
-        states.data_ptr<uint8_t>(), B, counts.data_ptr<int>(), n);
-}
 void accumulate_counts(torch::Tensor counts, torch::Tensor acc)
 {
     const int n = (int)counts.size(0);
     hipLaunchKernelGGL(accumulate_counts_kernel, dim3(1), dim3(WAVE), 0, cur_stream(),
         counts.data_ptr<int>(), (long long*)acc.data_ptr<int64_t>(), n);
 }
-void begin_tick(torch::Tensor states, torch::Tensor counts)
+static void launch_begin_tick(torch::Tensor& states, torch::Tensor& counts, int* first)
 {
     const int B = (int)states.size(0);
     const int n = (int)counts.size(0);
     const int blocks = (std::max(B, n) + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(begin_tick_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
-        states.data_ptr<uint8_t>(), B, counts.data_ptr<int>(), n, (int*)nullptr);
+        states.data_ptr<uint8_t>(), B, counts.data_ptr<int>(), n, first);
+}
+void begin_tick(torch::Tensor states, torch::Tensor counts)
+{
+    launch_begin_tick(states, counts, nullptr);
 }
 void begin_tick_first(torch::Tensor states, torch::Tensor counts, torch::Tensor first)
 {
-    const int B = (int)states.size(0);
-    const int n = (int)counts.size(0);
-    const int blocks = (std::max(B, n) + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(begin_tick_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
-        states.data_ptr<uint8_t>(), B, counts.data_ptr<int>(), n, first.data_ptr<int>());
+    launch_begin_tick(states, counts, first.data_ptr<int>());
 }
 void policy_first_match_mfma_into(
     torch::Tensor a_pack, torch::Tensor b_pack, torch::Tensor cards,
@@ -2280,13 +2272,19 @@ void compact_routable_spread(torch::Tensor allowed_slots, torch::Tensor allowed_
         routable_slots.data_ptr<int>(), routable_widx.data_ptr<int>(),
         routable_count.data_ptr<int>());
 }
+// a K5 chain as the kernels take it: four target states, -1 = unused
+static std::array<int, 4> unpack_chain(const std::vector<int64_t>& chain)
+{
+    std::array<int, 4> to = {-1, -1, -1, -1};
+    for (size_t c = 0; c < chain.size() && c < 4; ++c) to[c] = (int)chain[c];
+    return to;
+}
 void apply_transitions_chain_dyn(torch::Tensor states, torch::Tensor attempts,
                                  torch::Tensor deadlines, torch::Tensor slots,
                                  torch::Tensor count, std::vector<int64_t> chain,
                                  torch::Tensor extra_zero, int64_t capacity)
 {
-    int to[4] = {-1, -1, -1, -1};
-    for (size_t c = 0; c < chain.size() && c < 4; ++c) to[c] = (int)chain[c];
+    const auto to = unpack_chain(chain);
     const int n_extra = (int)extra_zero.size(0);
     const int blocks = (std::max((int)capacity, n_extra) + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(apply_transitions_chain_dyn_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
@@ -2446,8 +2444,7 @@ void tick_finish(torch::Tensor ctx_arena, torch::Tensor routable_slots,
                 "arenas must cover capacity slots");
     TORCH_CHECK(nwl > 0 && w_active_local.size(0) >= nwl, "w_active_local must be [nwl]");
     TORCH_CHECK(acc.size(0) >= counts.size(0) && counts.size(0) <= BLOCK, "acc must cover counts");
-    int to[4] = {-1, -1, -1, -1};
-    for (size_t c = 0; c < chain.size() && c < 4; ++c) to[c] = (int)chain[c];
+    const auto to = unpack_chain(chain);
     const int waves_per_block = BLOCK / WAVE;
     const int blocks = (std::max((int)capacity, 1) + waves_per_block - 1) / waves_per_block;
     hipLaunchKernelGGL(tick_finish_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
@@ -2902,7 +2899,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("policy_gate", &policy_gate, "decision gather + allow/deny compaction");
     m.def("policy_gate_full", &policy_gate_full,
           "gate + DENIED transition + DLQ ring append in one launch");
-    m.def("tick_reset", &tick_reset, "one-launch per-tick state/counter reset");
     m.def("begin_tick", &begin_tick, "tick prologue: PENDING re-admit + counter reset");
     m.def("accumulate_counts", &accumulate_counts, "fold tick counters into device accumulator");
     m.def("begin_tick_first", &begin_tick_first,

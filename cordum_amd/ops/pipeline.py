@@ -415,9 +415,17 @@ class _RefOps:
             dlq_ring[(h + k) % size] = j
         dlq_head[0] = h + len(appended)
 
-    def tick_reset(self, states, counts):
-        states.zero_()
-        counts.zero_()
+    def echo_execute_indexed_dyn(self, ctx_arena, slots, count, res_arena, res_sum,
+                                 stride, capacity):
+        from .reference import echo_execute_indexed_ref
+
+        echo_execute_indexed_ref(ctx_arena, slots[: int(count[0])], res_arena, res_sum,
+                                 int(stride))
+
+    def load_feedback(self, routable_widx, count, w_active_local, nwl, my_rank, capacity):
+        w = routable_widx[: int(count[0])].long()
+        mine = w[w // int(nwl) == int(my_rank)] % int(nwl)
+        w_active_local += torch.bincount(mine, minlength=w_active_local.shape[0]).to(torch.int32)
 
     def accumulate_counts(self, counts, acc):
         acc += counts.to(torch.int64)
@@ -828,7 +836,9 @@ class DevicePipeline:
 
     def _unfused_body(self, slot: int) -> None:
         """The tick as one kernel per stage (11-12 launches): what the fused
-        sequence replaced, kept as its test oracle."""
+        sequence replaced, kept as its test oracle. The GPU kernels of both
+        sequences share their stage bodies, so the oracle that shares no
+        code with the fused tick is this sequence on backend="ref" (CPU)."""
         B = self.B
         ext = self.ext
         jb = self.batches[slot]
@@ -903,8 +913,6 @@ class DevicePipeline:
         cost ever lands inside a timed step."""
         if self._graphs:
             return
-        if not hasattr(self, "_pend_states"):
-            self._pend_states = torch.full((self.B,), PENDING, dtype=torch.uint8, device=self.device)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -926,13 +934,18 @@ class DevicePipeline:
         self.acc_counts.zero_()
         torch.cuda.synchronize(self.device)
 
-    def _tick_fused(self) -> TickStats:
-        self._ensure_graphs()
-        t0 = time.perf_counter()
+    def _replay_fused(self) -> None:
+        """Replay the next ring slot's captured tick (graphs must exist) and
+        refresh the spread order; no host sync."""
         i = self._tick % len(self.batches)
         self._tick += 1
         self._graphs[i].replay()
         self._refresh_order()
+
+    def _tick_fused(self) -> TickStats:
+        self._ensure_graphs()
+        t0 = time.perf_counter()
+        self._replay_fused()
         counts = self._counts.cpu()  # one D2H read = the tick's only sync
         denied = int(counts[0])
         routable = int(counts[2])
@@ -978,6 +991,23 @@ class DevicePipeline:
             self._e2e_payloads.append(p.pin_memory() if pin else p)
         self._e2e_step = 0
 
+    def _encode_host(self, s: int, hb: JobBatch, enc: SyntheticEncoder,
+                     payload: torch.Tensor) -> None:
+        """Host-side preparation of batch `s`: a fresh encode into staging
+        batch `hb` plus the step stamp in word 0 of every `payload` row
+        (distinct content per step). Takes the fastest encoder the backend
+        has; all three produce the same batch for a given (seed, step) except
+        the torch one, which draws from its own generator."""
+        if hasattr(self.ext, "synthetic_fresh_stamped"):
+            # encode + payload stamp in one GIL-free native call
+            enc.fresh_stamped(hb, s, self.ext, payload, self.payload_words)
+            return
+        if hasattr(self.ext, "synthetic_fresh"):
+            enc.fresh_fast(hb, s, self.ext)
+        else:
+            enc.fresh(hb)
+        payload.view(self.B, self.payload_words)[:, 0] = s
+
     def tick_e2e(self) -> TickStats:
         """One serving-shaped tick: encode a FRESH random job batch on the
         host (vectorized, exact JobEncoder semantics), H2D the descriptors and
@@ -988,12 +1018,8 @@ class DevicePipeline:
         t0 = time.perf_counter()
         step = self._e2e_step
         self._e2e_step += 1
-        if hasattr(self.ext, "synthetic_fresh"):
-            self._e2e_enc.fresh_fast(self._e2e_host, step, self.ext)
-        else:
-            self._e2e_enc.fresh(self._e2e_host)
         payload = self._e2e_payloads[step % len(self._e2e_payloads)]
-        payload.view(self.B, self.payload_words)[:, 0] = step  # distinct content per step
+        self._encode_host(step, self._e2e_host, self._e2e_enc, payload)
         nb = self.device.type == "cuda"
         jb = self.batches[0]
         jb.any_bits.copy_(self._e2e_host.any_bits, non_blocking=nb)
@@ -1043,23 +1069,11 @@ class DevicePipeline:
         self._d_unrouted = 0  # conservation accounting for the dist tests
         lats = [0.0] * steps
         t_enc = [0.0] * steps
-        native = hasattr(self.ext, "synthetic_fresh")
-        stamped = hasattr(self.ext, "synthetic_fresh_stamped")
 
         def encode(s: int):
             t_enc[s] = time.perf_counter()
-            hb = self._d_hosts[s % nhost]
-            enc = self._d_encs[s % nhost]
-            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
-            if stamped:
-                # encode + payload stamp in one GIL-free native call
-                enc.fresh_stamped(hb, s, self.ext, payload, self.payload_words)
-                return
-            if native:
-                enc.fresh_fast(hb, s, self.ext)
-            else:
-                enc.fresh(hb)
-            payload.view(self.B, self.payload_words)[:, 0] = s
+            self._encode_host(s, self._d_hosts[s % nhost], self._d_encs[s % nhost],
+                              self._e2e_payloads[s % len(self._e2e_payloads)])
 
         fut = self._d_pool.submit(encode, 0)
         for s in range(steps):
@@ -1115,8 +1129,8 @@ class DevicePipeline:
             return completed, denied, lats
 
         self._ensure_graphs()
-        B, W = self.B, self.payload_words
-        nslots = 2   # device staging ring slots (graphs)
+        B = self.B
+        nslots = 2  # device staging ring slots (graphs)
         # host encode buffers. The reuse distance must clear the sync proof:
         # encode s+2 is submitted BEFORE harvest(s-1), so the buffer it
         # rewrites must have had its last H2D read by step s-2 (proven done
@@ -1153,23 +1167,10 @@ class DevicePipeline:
         lats = [0.0] * steps
         t_enc = [0.0] * steps
 
-        native_enc = hasattr(self.ext, "synthetic_fresh")
-        stamped_enc = hasattr(self.ext, "synthetic_fresh_stamped")
-
         def encode(s: int):
             t_enc[s] = time.perf_counter()
-            hb = self._e2e_hosts2[s % nhost]
-            enc = self._e2e_encs[s % nhost]
-            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
-            if stamped_enc:
-                # encode + payload stamp in one GIL-free native call
-                enc.fresh_stamped(hb, s, self.ext, payload, W)
-                return
-            if native_enc:
-                enc.fresh_fast(hb, s, self.ext)
-            else:
-                enc.fresh(hb)
-            payload.view(B, W)[:, 0] = s
+            self._encode_host(s, self._e2e_hosts2[s % nhost], self._e2e_encs[s % nhost],
+                              self._e2e_payloads[s % len(self._e2e_payloads)])
 
         def harvest(s_prev: int) -> None:
             nonlocal completed, denied
@@ -1247,34 +1248,12 @@ class DevicePipeline:
         tick() does is a self-imposed ~15 us graph-replay stall."""
         if getattr(self, "_fused_capable", False):
             self._ensure_graphs()
-            i = self._tick % len(self.batches)
-            self._tick += 1
-            self._graphs[i].replay()
-            self._refresh_order()
+            self._replay_fused()
             return
         if self.world > 1 and self.device.type == "cuda":
             self._pad_alloc()
             self._ensure_pad_graphs()
-            i = self._tick % len(self.batches)
-            self._tick += 1
-            if self._pad_graphs:
-                g1s, g2s, g3, g4 = self._pad_graphs
-                g1s[i].replay()
-                self._pad_heartbeats()
-                g2s[i].replay()
-                self._pad_exchange_out()
-                g3.replay()
-                self._pad_exchange_back()
-                g4.replay()
-            else:
-                self._pad_g1(i)
-                self._pad_heartbeats()
-                self._pad_g2(i)
-                self._pad_exchange_out()
-                self._pad_g3()
-                self._pad_exchange_back()
-                self._pad_g4()
-            self._refresh_order()
+            self._run_padded()
             return
         # CPU backends: run the stats-bearing tick and fold into the same
         # accumulator so collect_stats() is backend-uniform (the padded path
@@ -1505,39 +1484,39 @@ class DevicePipeline:
                   file=sys.stderr)
             self._pad_graphs = ()  # capture unsupported: stay eager
 
+    def _run_padded(self) -> None:
+        """The padded tick over the next ring slot: the four segments with
+        the collectives at their seams, replayed from the captured graphs
+        where there are any and run eagerly otherwise; then the spread-order
+        refresh. No host sync."""
+        i = self._tick % len(self.batches)
+        self._tick += 1
+        if self._pad_graphs:
+            g1s, g2s, g3, g4 = self._pad_graphs
+            g1, g2 = g1s[i].replay, g2s[i].replay
+            g3, g4 = g3.replay, g4.replay
+        else:
+            g1, g2 = (lambda: self._pad_g1(i)), (lambda: self._pad_g2(i))
+            g3, g4 = self._pad_g3, self._pad_g4
+        g1()
+        self._pad_heartbeats()
+        g2()
+        self._pad_exchange_out()
+        g3()
+        self._pad_exchange_back()
+        g4()
+        self._refresh_order()
+
     def _tick_padded(self) -> TickStats:
         """Cross-GPU dispatch with static shapes: per-destination segments of
         capacity B, counts as a device-resident vector exchanged with the
         payload — no host splits sync anywhere in the tick (the one
         `.cpu()` at the end is the stats read the bench needs anyway)."""
         self._pad_alloc()
-        use_graphs = False
         if self.device.type == "cuda":
             self._ensure_pad_graphs()
-            use_graphs = bool(self._pad_graphs)
         t0 = time.perf_counter()
-        i = self._tick % len(self.batches)
-        self._tick += 1
-        B = self.B
-        if use_graphs:
-            g1s, g2s, g3, g4 = self._pad_graphs
-            g1s[i].replay()
-            self._pad_heartbeats()
-            g2s[i].replay()
-            self._pad_exchange_out()
-            g3.replay()
-            self._pad_exchange_back()
-            g4.replay()
-            self._refresh_order()
-        else:
-            self._pad_g1(i)
-            self._pad_heartbeats()
-            self._pad_g2(i)
-            self._pad_exchange_out()
-            self._pad_g3()
-            self._pad_exchange_back()
-            self._pad_g4()
-            self._refresh_order()
+        self._run_padded()
         counts = self._counts.cpu()  # the tick's only host sync
         denied = int(counts[0])
         dispatched = int(counts[3])  # fresh + redelivered packed this tick

@@ -1,6 +1,8 @@
 """The fused 5-launch tick (prologue | K2 pick | K1 from bit words | gate+route
 | finish) against the one-kernel-per-stage sequence it replaced, on identical
-inputs; and K1-from-bits against the bitset K1 and the pack-then-MFMA path.
+inputs, run both on the GPU (same stage bodies, other kernels) and on the CPU
+reference backend (no shared code); and K1-from-bits against the bitset K1
+and the pack-then-MFMA path.
 
 Everything here is an integer path, so per-slot outputs must be EQUAL. The
 order of entries inside the compacted slot lists is unspecified (wave-level
@@ -68,22 +70,23 @@ def _mutate(pipe, case):
     pipe.order_buf.copy_(torch.arange(NW - 1, -1, -1, dtype=torch.int32, device=d))
 
 
-def _run(case, shape, unfused, ticks=2, **extra):
+def _run(case, shape, unfused, ticks=2, device=DEV, backend="ext", **extra):
     from cordum_amd.ops.pipeline import DevicePipeline
 
     B, R, NW, PW = shape
-    pipe = DevicePipeline(device=torch.device(DEV), batch_size=B, n_local_workers=NW,
+    pipe = DevicePipeline(device=torch.device(device), batch_size=B, n_local_workers=NW,
                           n_rules=R, n_batches=1, payload_words=PW, seed=3,
                           policy=_policy(case, R), mfma_pack_on_device=True,
-                          unfused_tick=unfused, **extra)
+                          unfused_tick=unfused, backend=backend, **extra)
     _mutate(pipe, case)
+    sync = torch.cuda.synchronize if pipe.device.type == "cuda" else (lambda: None)
     mid = None
     for t in range(ticks):
         pipe._fused_body(0)
         if t == 0:
-            torch.cuda.synchronize()
+            sync()
             mid = pipe.w_active_local.cpu().clone()
-    torch.cuda.synchronize()
+    sync()
     return pipe, mid
 
 
@@ -120,15 +123,10 @@ def _compare(new, old, mid_new, mid_old):
     return n_den, n_all, n_rt
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "B%d-R%d-W%d-P%d" % s)
-@pytest.mark.parametrize("case", CASES)
-def test_fused_tick_equals_unfused(case, shape):
-    new, mid_new = _run(case, shape, unfused=False)
-    assert new._use_mfma, "shape must exercise the MFMA K1-from-bits path"
-    old, mid_old = _run(case, shape, unfused=True)
-    n_den, n_all, n_rt = _compare(new, old, mid_new, mid_old)
+def _check_case(case, shape, counts, mid_new):
+    """The case must actually be the case."""
+    n_den, n_all, n_rt = counts
     B = shape[0]
-    # the case must actually be the case
     if case == "deny_all":
         assert n_den == B and n_rt == 0
     elif case == "deny_none":
@@ -140,6 +138,30 @@ def test_fused_tick_equals_unfused(case, shape):
         assert int(mid_new.max()) == int(mid_new.sum()) == n_all
     elif case == "labels" and shape[2] >= 4 and B >= 5:
         assert n_rt > 0 and int((mid_new > 0).sum()) > 1
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "B%d-R%d-W%d-P%d" % s)
+@pytest.mark.parametrize("case", CASES)
+def test_fused_tick_equals_unfused(case, shape):
+    new, mid_new = _run(case, shape, unfused=False)
+    assert new._use_mfma, "shape must exercise the MFMA K1-from-bits path"
+    old, mid_old = _run(case, shape, unfused=True)
+    _check_case(case, shape, _compare(new, old, mid_new, mid_old), mid_new)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "B%d-R%d-W%d-P%d" % s)
+@pytest.mark.parametrize("case", CASES)
+def test_fused_tick_equals_cpu_reference(case, shape):
+    """The fused and staged GPU kernels share their stage bodies, so a fault
+    in a body shows identically on both sides of the test above. The staged
+    tick on the CPU reference backend shares no code with them: same
+    arguments, same set-up, same comparison. Every compared field is an
+    integer path except w_keys, whose score goes through float; it is
+    compared with the worker loads as they are."""
+    new, mid_new = _run(case, shape, unfused=False)
+    assert new._use_mfma, "shape must exercise the MFMA K1-from-bits path"
+    ref, mid_ref = _run(case, shape, unfused=True, device="cpu", backend="ref")
+    _check_case(case, shape, _compare(new, ref, mid_new, mid_ref), mid_new)
 
 
 @pytest.mark.parametrize("shape", [(257, 17, 64, 65), (1000, 300, 1025, 1)],
