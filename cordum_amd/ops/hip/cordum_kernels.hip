@@ -800,10 +800,21 @@ __global__ __launch_bounds__(BLOCK) void wf_expand_kernel(
         // ordinal stream identical on every backend regardless of atomic
         // packing order (retried children get FRESH ordinals)
         seq0 = children_emitted[rs];
-        if (todo > 0) {
+        if (todo > CB) {
+            // can never fit: leave the counter alone, so the entry cannot
+            // push the ones that do fit out of the arena
+            todo = -1;
+        } else if (todo > 0) {
             base = atomicAdd(child_count, todo);
-            if (base + todo > CB) {      // arena full: roll back, retry later
-                atomicSub(child_count, todo);
+            if (base + todo > CB) {
+                // arena full: roll back, retry later. A failed add leaves
+                // the counter above CB, so nothing is granted until it is
+                // lowered, and the lowest failed base is the end of the
+                // granted ranges: atomicMin restores exactly that. (Taking
+                // only the own todo back, as atomicSub did, kept the other
+                // failed adds in the counter, and the next grant reserved a
+                // range past the final count, with a hole below it.)
+                atomicMin(child_count, base);
                 todo = -1;
             } else {
                 step_state[rs] = WFS_DISPATCHED;
@@ -1000,7 +1011,9 @@ __global__ __launch_bounds__(BLOCK) void wf_commit_kernel(
             step_attempts[i] += 1;
             children_todo[i] += fail;      // only failed children re-run
             children_fail[i] = 0;
-            next_ready[i] = *tick_p + min(1 << step_attempts[i], 16);
+            // backoff min(2^attempts, 16): the shift is capped at 4 so an
+            // attempt count past the width of an int cannot wrap the delay
+            next_ready[i] = *tick_p + (1 << min(step_attempts[i], 4));
             step_state[i] = WFS_PENDING;
             atomicAdd(retry_count, (unsigned long long)fail);
         } else {

@@ -483,6 +483,105 @@ def test_fused_tick_kernels_match_refops(ext):
     assert acc.cpu().tolist() == [2, 4, 6, 8]
 
 
+DLQ_RING, DLQ_POISON = 64, -7
+
+
+def _ring_cells(head0, n):
+    return sorted({(head0 + k) % DLQ_RING for k in range(n)})
+
+
+@pytest.mark.parametrize("head0", [59, DLQ_RING + 59])
+def test_dlq_ring_append_wraps(ext, head0):
+    """20 slots appended at head 59 of a 64-deep ring: the cells
+    (head0 .. head0+19) % 64 hold exactly the 20 slots, the rest is untouched."""
+    from cordum_amd.ops.pipeline import _RefOps
+
+    n = 20
+    slots = torch.arange(40, dtype=torch.int32) * 3 + 1000  # 20 live, 20 past count
+    count = torch.tensor([n], dtype=torch.int32)
+    ring_r = torch.full((DLQ_RING,), DLQ_POISON, dtype=torch.int32)
+    head_r = torch.tensor([head0], dtype=torch.int32)
+    _RefOps().dlq_ring_append(slots, count, ring_r, head_r, slots.numel())
+    cells = _ring_cells(head0, n)
+    assert len(cells) == n and min(cells) == 0 and max(cells) == DLQ_RING - 1  # it wraps
+    assert int(head_r[0]) == head0 + n
+
+    d = dev()
+    ring = torch.full((DLQ_RING,), DLQ_POISON, dtype=torch.int32, device=d)
+    head = torch.tensor([head0], dtype=torch.int32, device=d)
+    ext.dlq_ring_append(slots.to(d), count.to(d), ring, head, slots.numel())
+    ring = ring.cpu()
+    assert int(head.cpu()[0]) == int(head_r[0])
+    assert sorted(ring[cells].tolist()) == sorted(ring_r[cells].tolist()) == slots[:n].tolist()
+    rest = [c for c in range(DLQ_RING) if c not in cells]
+    assert ring[rest].tolist() == [DLQ_POISON] * len(rest)
+    assert torch.equal(ring[rest], ring_r[rest])
+
+
+def test_dlq_ring_append_more_than_the_ring(ext):
+    """300 slots into a 64-deep ring: every cell holds one of them."""
+    n, head0 = 300, 59
+    slots = torch.arange(n, dtype=torch.int32) * 3 + 1000
+    d = dev()
+    ring = torch.full((DLQ_RING,), DLQ_POISON, dtype=torch.int32, device=d)
+    head = torch.tensor([head0], dtype=torch.int32, device=d)
+    ext.dlq_ring_append(slots.to(d), torch.tensor([n], dtype=torch.int32, device=d),
+                        ring, head, n)
+    assert int(head.cpu()[0]) == head0 + n
+    assert set(ring.cpu().tolist()) <= set(slots.tolist())
+
+
+@pytest.mark.parametrize("B", [70, 2048])
+def test_policy_gate_full_dlq_ring_wraps(ext, B):
+    """The fused gate's DENIED -> DLQ append on a 64-deep ring at head 59:
+    B=70 wraps inside the ring, B=2048 laps it many times."""
+    from cordum_amd.ops.pipeline import _RefOps
+
+    g = torch.Generator().manual_seed(19 + B)
+    R, head0 = 96, 59
+    ref = _RefOps()
+    lut = torch.tensor(transition_lut(), dtype=torch.uint8).flatten()
+    ref.set_transition_lut(lut)
+    ext.set_transition_lut(lut)
+    first = torch.where(torch.rand(B, generator=g) < 0.7,
+                        torch.randint(0, R, (B,), dtype=torch.int32, generator=g),
+                        torch.tensor(2**31 - 1, dtype=torch.int32))
+    decisions = torch.randint(1, 6, (R,), dtype=torch.int8, generator=g)
+    deadlines0 = torch.randint(1, 2**40, (B,), dtype=torch.int64, generator=g)
+
+    def gate_state(dev_):
+        return {"states": torch.ones(B, dtype=torch.uint8, device=dev_),  # PENDING
+                "deadlines": deadlines0.to(dev_, copy=True),
+                "out_dec": torch.zeros(B, dtype=torch.int8, device=dev_),
+                "ds": torch.zeros(B, dtype=torch.int32, device=dev_),
+                "als": torch.zeros(B, dtype=torch.int32, device=dev_),
+                "cnt": torch.zeros(4, dtype=torch.int32, device=dev_),
+                "ring": torch.full((DLQ_RING,), DLQ_POISON, dtype=torch.int32, device=dev_),
+                "head": torch.tensor([head0], dtype=torch.int32, device=dev_)}
+
+    def run(ops, s, dev_):
+        ops.policy_gate_full(first.to(dev_), decisions.to(dev_), s["out_dec"], s["ds"],
+                             s["cnt"][0:1], s["als"], s["cnt"][1:2], s["states"],
+                             s["deadlines"], s["ring"], s["head"])
+        return {k: v.cpu() for k, v in s.items()}
+
+    want = run(ref, gate_state("cpu"), "cpu")
+    got = run(ext, gate_state(dev()), dev())
+    n = int(want["head"][0]) - head0
+    denied = sorted(want["ds"][:n].tolist())
+    assert n == int(want["cnt"][0]) and n > (DLQ_RING if B == 2048 else DLQ_RING - head0)
+    for k in ("states", "deadlines", "out_dec", "cnt", "head"):
+        assert torch.equal(got[k], want[k]), k
+    if n <= DLQ_RING:
+        cells = _ring_cells(head0, n)
+        assert sorted(got["ring"][cells].tolist()) == denied
+        rest = [c for c in range(DLQ_RING) if c not in cells]
+        assert got["ring"][rest].tolist() == [DLQ_POISON] * len(rest)
+    else:  # lapped: every cell holds a denied job, no two cells the same one
+        cells = got["ring"].tolist()
+        assert set(cells) <= set(denied) and len(set(cells)) == DLQ_RING
+
+
 def test_pack_jobs_mfma_device_matches_host(ext):
     """The device A-fragment packing must equal policy_mfma.pack_jobs_mfma
     byte-for-byte (same fragment layout the matrix cores consume)."""
