@@ -1075,6 +1075,280 @@ __global__ __launch_bounds__(BLOCK) void wf_grant_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K3-WF run lifecycle: admit / cancel / retire between ticks
+// ---------------------------------------------------------------------------
+// Dynamic mode of the workflow engine: a run slot is FREE, LIVE (admitted,
+// running or terminal-but-unreported) or DRAINING (terminal and reported,
+// children may still be parked in the requeue ring). A host handle is
+// (slot, generation); run_gen[slot] increments at each admission, so a stale
+// handle can never cancel the slot's next occupant (CancelRun analog,
+// workflow/engine.go:349-451). All three kernels run between ticks, outside
+// the captured graph, and read the device tick counter.
+//
+// Invariant: a slot is never handed to a new run while a child of its
+// previous occupant can still be applied to it. wf_retire frees a DRAINING
+// row only when every step has no child out, or its last expansion is older
+// than the timeout cutoff, which exceeds the longest requeue-ring lifetime.
+//
+// A cancelled step is WFS_CANCELLED: sweep, expand, timeout scan, commit and
+// status only ever act on the states 0..5 they name, so they leave it alone.
+#define WFS_CANCELLED 6
+#define WFL_FREE 0
+#define WFL_LIVE 1
+#define WFL_DRAINING 2
+
+// admission pass 1: free-slot bitmask per wave (4 per 256-slot block) and
+// the free count per block. The masks are a snapshot: the admit pass reads
+// them, never run_life, so its waves cannot race on the table they fill.
+__global__ __launch_bounds__(BLOCK) void wf_admit_count_kernel(
+    const unsigned char* __restrict__ run_life,   // [NR]
+    unsigned long long* __restrict__ free_mask,   // [nblk*4]
+    int* __restrict__ blk_scan,                   // [nblk+1] counts, scanned next
+    int NR)
+{
+    __shared__ int cnt[BLOCK / WAVE];
+    const int run = blockIdx.x * BLOCK + threadIdx.x;
+    const int w = threadIdx.x / WAVE;
+    const unsigned long long m =
+        __ballot(run < NR && run_life[run] == WFL_FREE);
+    if (threadIdx.x % WAVE == 0) {
+        free_mask[(size_t)blockIdx.x * (BLOCK / WAVE) + w] = m;
+        cnt[w] = __popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        blk_scan[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+// admission pass 2: in-place exclusive scan of the block counts by one
+// workgroup (4096 entries at one million slots); blk_scan[nblk] = total free
+__global__ __launch_bounds__(BLOCK) void wf_admit_scan_kernel(
+    int* __restrict__ blk_scan, int nblk)
+{
+    __shared__ int part[BLOCK];
+    const int chunk = (nblk + BLOCK - 1) / BLOCK;
+    const int lo = min((int)threadIdx.x * chunk, nblk);
+    const int hi = min(lo + chunk, nblk);
+    int sum = 0;
+    for (int j = lo; j < hi; ++j) sum += blk_scan[j];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int t = 0; t < BLOCK; ++t) { const int v = part[t]; part[t] = run; run += v; }
+        blk_scan[nblk] = run;
+    }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int j = lo; j < hi; ++j) { const int v = blk_scan[j]; blk_scan[j] = run; run += v; }
+}
+
+// admission pass 3: one wave per request. Request i takes the i-th lowest
+// FREE slot (binary search over the scanned block counts, then popcounts
+// over the block's four masks), a pure function of the tables and the
+// request order. Its 64 lanes write the 64-step row, one lane per step, so
+// every table write is one coalesced 64-lane store.
+__global__ __launch_bounds__(BLOCK) void wf_admit_kernel(
+    const int* __restrict__ req_tmpl,             // [n] template id
+    const long long* __restrict__ req_cond,       // [n] condition bits
+    const int* __restrict__ req_fanout,           // [n] FOR_EACH override (0 = none)
+    int n,
+    const long long* __restrict__ tmpl_deps,      // [TC*64]
+    const unsigned char* __restrict__ tmpl_kind,  // [TC*64]
+    const int* __restrict__ tmpl_todo,            // [TC*64]
+    const int* __restrict__ tmpl_maxp,            // [TC*64]
+    const int* __restrict__ tmpl_delay,           // [TC*64]
+    const unsigned char* __restrict__ tmpl_nsteps,// [TC]
+    int TC,
+    const unsigned long long* __restrict__ free_mask,
+    const int* __restrict__ blk_scan, int nblk,
+    unsigned char* __restrict__ step_state,
+    int* __restrict__ step_attempts,
+    long long* __restrict__ deps_mask,
+    unsigned char* __restrict__ step_kind,
+    int* __restrict__ children_todo,
+    int* __restrict__ max_parallel,
+    int* __restrict__ children_out,
+    int* __restrict__ children_done,
+    int* __restrict__ children_fail,
+    int* __restrict__ children_emitted,
+    int* __restrict__ next_ready,
+    int* __restrict__ dispatch_tick,
+    unsigned char* __restrict__ n_steps,
+    long long* __restrict__ cond_bits,
+    unsigned char* __restrict__ run_state,
+    unsigned char* __restrict__ run_active,
+    unsigned char* __restrict__ run_life,
+    int* __restrict__ run_gen,
+    const int* __restrict__ tick_p,
+    int* __restrict__ out_slot,                   // [n]
+    int* __restrict__ out_gen,                    // [n]
+    unsigned long long* __restrict__ admit_count,
+    int NR)
+{
+    const int i = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    if (i >= n) return;                           // wave-uniform
+    const int total = blk_scan[nblk];
+    if (i == 0 && lane == 0)
+        atomicAdd(admit_count, (unsigned long long)min(n, total));
+    if (i >= total) {                             // table full
+        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
+        return;
+    }
+    // largest block b with blk_scan[b] <= i (empty blocks share a prefix)
+    int lo = 0, hi = nblk - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk_scan[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    int k = i - blk_scan[lo];
+    int g = 0;
+    unsigned long long m = free_mask[(size_t)lo * 4];
+    while (g < 3 && k >= __popcll(m)) {
+        k -= __popcll(m);
+        ++g;
+        m = free_mask[(size_t)lo * 4 + g];
+    }
+    // the k-th set bit of m: the one lane whose bit is set with k below it
+    const unsigned long long pick = __ballot(
+        ((m >> lane) & 1ull) && __popcll(m & ((1ull << lane) - 1ull)) == k);
+    const int slot = lo * BLOCK + g * WAVE + (__ffsll((long long)pick) - 1);
+    if (pick == 0ull || slot >= NR) {             // cannot happen: masks and scan agree
+        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
+        return;
+    }
+
+    const int tid = req_tmpl[i];
+    const bool known = tid >= 0 && tid < TC;      // host rejects the rest
+    const int ns = known ? (int)tmpl_nsteps[tid] : 0;
+    const int tick1 = *tick_p + 1;                // the run's first tick
+    const bool in = lane < ns;
+    const size_t ti = (size_t)(known ? tid : 0) * 64 + lane;
+    const size_t ri = (size_t)slot * 64 + lane;
+    const int kind = in ? (int)tmpl_kind[ti] : 0;
+    const int fan = req_fanout[i];
+    step_state[ri] = WFS_PENDING;
+    step_attempts[ri] = 0;
+    deps_mask[ri] = in ? tmpl_deps[ti] : 0ll;
+    step_kind[ri] = (unsigned char)kind;
+    children_todo[ri] = !in ? 0 : (kind == WFK_FOR_EACH && fan > 0) ? fan : tmpl_todo[ti];
+    max_parallel[ri] = in ? tmpl_maxp[ti] : 0;
+    children_out[ri] = 0;
+    children_done[ri] = 0;
+    children_fail[ri] = 0;
+    children_emitted[ri] = 0;
+    next_ready[ri] = in ? tick1 + tmpl_delay[ti] : 0;
+    dispatch_tick[ri] = in ? tick1 : 0;
+    if (lane == 0) {
+        n_steps[slot] = (unsigned char)ns;
+        cond_bits[slot] = req_cond[i];
+        run_state[slot] = 0;
+        run_active[slot] = 1;
+        run_life[slot] = WFL_LIVE;
+        const int gen = run_gen[slot] + 1;
+        run_gen[slot] = gen;
+        out_slot[i] = slot;
+        out_gen[i] = gen;
+    }
+}
+
+// cancellation: one wave per request (distinct slots), one lane per step.
+// Effective only on a LIVE, still-active run of the named generation; the
+// child counters are left alone, so children in flight still apply into the
+// quarantined row and the retire pass can tell when it is quiet.
+__global__ __launch_bounds__(BLOCK) void wf_cancel_kernel(
+    const int* __restrict__ req_slot,             // [n]
+    const int* __restrict__ req_gen,              // [n]
+    int n,
+    const unsigned char* __restrict__ run_life,
+    const int* __restrict__ run_gen,
+    unsigned char* __restrict__ run_active,
+    unsigned char* __restrict__ run_state,
+    const unsigned char* __restrict__ n_steps,
+    unsigned char* __restrict__ step_state,
+    unsigned long long* __restrict__ cancel_count,
+    unsigned char* __restrict__ out_ok,           // [n]
+    int NR)
+{
+    const int i = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    if (i >= n) return;                           // wave-uniform
+    const int slot = req_slot[i];
+    int ok = 0;
+    if (lane == 0 && slot >= 0 && slot < NR)
+        ok = run_life[slot] == WFL_LIVE && run_gen[slot] == req_gen[i]
+             && run_active[slot] == 1;
+    ok = __shfl(ok, 0, WAVE);
+    if (!ok) {
+        if (lane == 0) out_ok[i] = 0;
+        return;
+    }
+    if (lane < (int)n_steps[slot]) {
+        const size_t ri = (size_t)slot * 64 + lane;
+        const unsigned char s = step_state[ri];
+        if (s == WFS_PENDING || s == WFS_DISPATCHED || s == WFS_WAITING)
+            step_state[ri] = WFS_CANCELLED;
+    }
+    if (lane == 0) {
+        run_active[slot] = 0;
+        run_state[slot] = WFS_CANCELLED;
+        out_ok[i] = 1;
+        atomicAdd(cancel_count, 1ull);
+    }
+}
+
+// retirement: one thread per run for the one-byte life filter; terminal LIVE
+// runs are appended to the done list (wave-aggregated, order undefined) and
+// become DRAINING. Each DRAINING run, including one set just now, gets a
+// wave-cooperative row check: all 64 lanes read the chosen run's row. A
+// call that finds few terminal runs reads the life bytes, not the rows.
+__global__ __launch_bounds__(BLOCK) void wf_retire_kernel(
+    unsigned char* __restrict__ run_life,         // [NR]
+    const unsigned char* __restrict__ run_active,
+    const unsigned char* __restrict__ run_state,
+    const int* __restrict__ run_gen,
+    const unsigned char* __restrict__ n_steps,
+    const int* __restrict__ children_out,         // [NR*64]
+    const int* __restrict__ dispatch_tick,        // [NR*64]
+    const int* __restrict__ tick_p, int cutoff,
+    int* __restrict__ done_slot,                  // [cap]
+    int* __restrict__ done_gen,
+    int* __restrict__ done_state,
+    int* __restrict__ done_count,                 // [1]
+    int NR, int cap)
+{
+    const int run = blockIdx.x * BLOCK + threadIdx.x;
+    const int lane = threadIdx.x % WAVE;
+    const int life = run < NR ? (int)run_life[run] : WFL_FREE;
+    const bool report = life == WFL_LIVE && run_active[run] == 0;
+    const int pos = wave_append_slot(report, done_count, lane);
+    if (pos >= 0 && pos < cap) {
+        done_slot[pos] = run;
+        done_gen[pos] = run_gen[run];
+        done_state[pos] = run_state[run];
+    }
+    const bool draining = report || life == WFL_DRAINING;
+    const int stale = *tick_p - cutoff;
+    unsigned long long todo = __ballot(draining);
+    bool quiet = false;
+    while (todo != 0ull) {                        // wave-uniform loop
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const int r = __shfl(run, src, WAVE);
+        const size_t ri = (size_t)r * 64 + lane;
+        const bool blocking = lane < (int)n_steps[r] && children_out[ri] > 0
+                              && dispatch_tick[ri] > stale;
+        const bool q = !__any(blocking);
+        if (lane == src) quiet = q;
+    }
+    if (draining) {
+        const int next = quiet ? WFL_FREE : WFL_DRAINING;
+        if (next != life) run_life[run] = (unsigned char)next;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K4: deadline / staleness scan -> TIMEOUT candidates (compacted list)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void deadline_scan_kernel(
@@ -2683,6 +2957,111 @@ void wf_grant(torch::Tensor grant_runs, torch::Tensor grant_steps, torch::Tensor
         verdicts.data_ptr<uint8_t>(), (int)n, step_state.data_ptr<uint8_t>());
 }
 
+// three launches on the current stream: free-slot masks + block counts, the
+// scan of the counts, then one wave per request. free_mask / blk_scan are
+// caller-owned workspaces ([nblk*4] int64, [nblk+1] int32, nblk = ceil(NR/256))
+void wf_admit(torch::Tensor req_tmpl, torch::Tensor req_cond, torch::Tensor req_fanout,
+              torch::Tensor tmpl_deps, torch::Tensor tmpl_kind, torch::Tensor tmpl_todo,
+              torch::Tensor tmpl_maxp, torch::Tensor tmpl_delay, torch::Tensor tmpl_nsteps,
+              torch::Tensor step_state, torch::Tensor step_attempts,
+              torch::Tensor deps_mask, torch::Tensor step_kind,
+              torch::Tensor children_todo, torch::Tensor max_parallel,
+              torch::Tensor children_out, torch::Tensor children_done,
+              torch::Tensor children_fail, torch::Tensor children_emitted,
+              torch::Tensor next_ready, torch::Tensor dispatch_tick,
+              torch::Tensor n_steps, torch::Tensor cond_bits,
+              torch::Tensor run_state, torch::Tensor run_active,
+              torch::Tensor run_life, torch::Tensor run_gen, torch::Tensor tick,
+              torch::Tensor free_mask, torch::Tensor blk_scan,
+              torch::Tensor out_slot, torch::Tensor out_gen, torch::Tensor admit_count)
+{
+    const int n = (int)req_tmpl.size(0);
+    if (n <= 0) return;
+    const int NR = (int)n_steps.size(0);
+    const int nblk = (NR + BLOCK - 1) / BLOCK;
+    TORCH_CHECK(req_cond.size(0) >= n && req_fanout.size(0) >= n
+                && out_slot.size(0) >= n && out_gen.size(0) >= n,
+                "wf_admit: request/output arrays shorter than the request count");
+    TORCH_CHECK(free_mask.numel() >= (int64_t)nblk * (BLOCK / WAVE)
+                && blk_scan.numel() >= nblk + 1, "wf_admit: workspace too small");
+    TORCH_CHECK(step_state.numel() == (int64_t)NR * 64 && run_life.numel() == NR
+                && run_gen.numel() == NR, "wf_admit: table sizes disagree");
+    const int TC = (int)tmpl_nsteps.size(0);
+    TORCH_CHECK(tmpl_deps.numel() == (int64_t)TC * 64, "wf_admit: template sizes disagree");
+    hipLaunchKernelGGL(wf_admit_count_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
+        run_life.data_ptr<uint8_t>(),
+        (unsigned long long*)free_mask.data_ptr<int64_t>(), blk_scan.data_ptr<int>(), NR);
+    hipLaunchKernelGGL(wf_admit_scan_kernel, dim3(1), dim3(BLOCK), 0, cur_stream(),
+        blk_scan.data_ptr<int>(), nblk);
+    const int blocks = (n + (BLOCK / WAVE) - 1) / (BLOCK / WAVE);
+    hipLaunchKernelGGL(wf_admit_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        req_tmpl.data_ptr<int>(), (const long long*)req_cond.data_ptr<int64_t>(),
+        req_fanout.data_ptr<int>(), n,
+        (const long long*)tmpl_deps.data_ptr<int64_t>(), tmpl_kind.data_ptr<uint8_t>(),
+        tmpl_todo.data_ptr<int>(), tmpl_maxp.data_ptr<int>(), tmpl_delay.data_ptr<int>(),
+        tmpl_nsteps.data_ptr<uint8_t>(), TC,
+        (const unsigned long long*)free_mask.data_ptr<int64_t>(),
+        blk_scan.data_ptr<int>(), nblk,
+        step_state.data_ptr<uint8_t>(), step_attempts.data_ptr<int>(),
+        (long long*)deps_mask.data_ptr<int64_t>(), step_kind.data_ptr<uint8_t>(),
+        children_todo.data_ptr<int>(), max_parallel.data_ptr<int>(),
+        children_out.data_ptr<int>(), children_done.data_ptr<int>(),
+        children_fail.data_ptr<int>(), children_emitted.data_ptr<int>(),
+        next_ready.data_ptr<int>(), dispatch_tick.data_ptr<int>(),
+        n_steps.data_ptr<uint8_t>(), (long long*)cond_bits.data_ptr<int64_t>(),
+        run_state.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
+        run_life.data_ptr<uint8_t>(), run_gen.data_ptr<int>(), tick.data_ptr<int>(),
+        out_slot.data_ptr<int>(), out_gen.data_ptr<int>(),
+        (unsigned long long*)admit_count.data_ptr<int64_t>(), NR);
+}
+
+void wf_cancel(torch::Tensor req_slot, torch::Tensor req_gen,
+               torch::Tensor run_life, torch::Tensor run_gen,
+               torch::Tensor run_active, torch::Tensor run_state,
+               torch::Tensor n_steps, torch::Tensor step_state,
+               torch::Tensor cancel_count, torch::Tensor out_ok)
+{
+    const int n = (int)req_slot.size(0);
+    if (n <= 0) return;
+    const int NR = (int)n_steps.size(0);
+    TORCH_CHECK(req_gen.size(0) >= n && out_ok.size(0) >= n,
+                "wf_cancel: request/output arrays shorter than the request count");
+    TORCH_CHECK(step_state.numel() == (int64_t)NR * 64 && run_life.numel() == NR
+                && run_gen.numel() == NR, "wf_cancel: table sizes disagree");
+    const int blocks = (n + (BLOCK / WAVE) - 1) / (BLOCK / WAVE);
+    hipLaunchKernelGGL(wf_cancel_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        req_slot.data_ptr<int>(), req_gen.data_ptr<int>(), n,
+        run_life.data_ptr<uint8_t>(), run_gen.data_ptr<int>(),
+        run_active.data_ptr<uint8_t>(), run_state.data_ptr<uint8_t>(),
+        n_steps.data_ptr<uint8_t>(), step_state.data_ptr<uint8_t>(),
+        (unsigned long long*)cancel_count.data_ptr<int64_t>(),
+        out_ok.data_ptr<uint8_t>(), NR);
+}
+
+void wf_retire(torch::Tensor run_life, torch::Tensor run_active, torch::Tensor run_state,
+               torch::Tensor run_gen, torch::Tensor n_steps,
+               torch::Tensor children_out, torch::Tensor dispatch_tick,
+               torch::Tensor tick, int64_t cutoff,
+               torch::Tensor done_slot, torch::Tensor done_gen,
+               torch::Tensor done_state, torch::Tensor done_count)
+{
+    const int NR = (int)n_steps.size(0);
+    const int cap = (int)done_slot.size(0);
+    TORCH_CHECK(done_gen.size(0) >= cap && done_state.size(0) >= cap,
+                "wf_retire: done arrays disagree");
+    TORCH_CHECK(children_out.numel() == (int64_t)NR * 64 && run_life.numel() == NR
+                && dispatch_tick.numel() == (int64_t)NR * 64,
+                "wf_retire: table sizes disagree");
+    const int blocks = (NR + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(wf_retire_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        run_life.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
+        run_state.data_ptr<uint8_t>(), run_gen.data_ptr<int>(),
+        n_steps.data_ptr<uint8_t>(), children_out.data_ptr<int>(),
+        dispatch_tick.data_ptr<int>(), tick.data_ptr<int>(), (int)cutoff,
+        done_slot.data_ptr<int>(), done_gen.data_ptr<int>(),
+        done_state.data_ptr<int>(), done_count.data_ptr<int>(), NR, cap);
+}
+
 void materialize_rq_payload(torch::Tensor payload, torch::Tensor rq_prev_payload,
                             torch::Tensor rq_src, torch::Tensor rq_count,
                             torch::Tensor rq_payload, int64_t stride)
@@ -2966,6 +3345,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_readmit", &wf_readmit, "K3-WF continuous run re-admission from template");
     m.def("wf_status", &wf_status, "K3-WF run status roll-up");
     m.def("wf_grant", &wf_grant, "K3-WF host approval grants");
+    m.def("wf_admit", &wf_admit, "K3-WF run admission into the lowest free slots");
+    m.def("wf_cancel", &wf_cancel, "K3-WF generation-checked run cancellation");
+    m.def("wf_retire", &wf_retire, "K3-WF completion records + quiescent slot release");
     m.def("materialize_rq_payload", &materialize_rq_payload, "copy requeued payload rows into the rq arena");
     m.def("gather_payload_padded", &gather_payload_padded, "payload gather into padded send arena");
     m.def("echo_padded", &echo_padded, "region-valid echo over padded recv arena");

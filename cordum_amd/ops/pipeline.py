@@ -329,6 +329,21 @@ class _RefOps:
         args[14] = int(args[14])  # filter_state
         wf_readmit_ref(*args)
 
+    def wf_admit(self, *a):
+        from .reference import wf_admit_ref
+
+        wf_admit_ref(*a)
+
+    def wf_cancel(self, *a):
+        from .reference import wf_cancel_ref
+
+        wf_cancel_ref(*a)
+
+    def wf_retire(self, rl, ra, rs, rg, ns, co, dt, tick, cutoff, ds, dg, dst, dc):
+        from .reference import wf_retire_ref
+
+        wf_retire_ref(rl, ra, rs, rg, ns, co, dt, tick, int(cutoff), ds, dg, dst, dc)
+
     def materialize_rq_payload(self, payload, prev_payload, rq_src, rq_count,
                                rq_payload, stride):
         from .reference import materialize_rq_payload_ref

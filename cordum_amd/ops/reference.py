@@ -554,3 +554,119 @@ def wf_readmit_ref(run_active, run_state, n_steps, step_state, step_attempts,
         run_state[run] = 0
         run_active[run] = 1
         admit_count[0] += 1
+
+
+# -- K3-WF run lifecycle references (dynamic mode: admit / cancel / retire) ----
+# Life states of a run slot; a cancelled run or step is WFS_CANCELLED, a code
+# the tick kernels never act on.
+
+WFS_CANCELLED = 6
+WFL_FREE, WFL_LIVE, WFL_DRAINING = 0, 1, 2
+
+
+def wf_admit_ref(req_tmpl, req_cond, req_fanout,
+                 tmpl_deps, tmpl_kind, tmpl_todo, tmpl_maxp, tmpl_delay,
+                 tmpl_nsteps,
+                 step_state, step_attempts, deps_mask, step_kind,
+                 children_todo, max_parallel, children_out, children_done,
+                 children_fail, children_emitted, next_ready, dispatch_tick,
+                 n_steps, cond_bits, run_state, run_active, run_life, run_gen,
+                 tick, free_mask, blk_scan, out_slot, out_gen, admit_count):
+    """Request i takes the i-th lowest FREE slot; requests past the free count
+    get slot -1. free_mask / blk_scan are the kernel's workspaces: unused."""
+    n = int(req_tmpl.shape[0])
+    if n <= 0:
+        return
+    NR = int(n_steps.shape[0])
+    TC = int(tmpl_nsteps.shape[0])
+    tick1 = int(tick[0]) + 1  # the run's first tick
+    free = torch.nonzero(run_life[:NR] == WFL_FREE).flatten().tolist()  # ascending
+    admit_count[0] += min(n, len(free))
+    for i in range(n):
+        if i >= len(free):
+            out_slot[i] = -1
+            out_gen[i] = 0
+            continue
+        slot = free[i]
+        tid = int(req_tmpl[i])
+        known = 0 <= tid < TC  # the host rejects the rest
+        ns = int(tmpl_nsteps[tid]) if known else 0
+        fan = int(req_fanout[i])
+        # the whole 64-entry row, one element per step (the kernel's lanes):
+        # steps s < ns from the template, the rest zero
+        row = slice(slot * 64, slot * 64 + 64)
+        trow = slice((tid if known else 0) * 64, (tid if known else 0) * 64 + 64)
+        inside = torch.arange(64) < ns
+        kind = torch.where(inside, tmpl_kind[trow], 0)
+        todo = tmpl_todo[trow]
+        if fan > 0:
+            todo = torch.where(kind == WFK_FOR_EACH, fan, todo)
+        step_state[row] = WFS_PENDING
+        step_attempts[row] = 0
+        deps_mask[row] = torch.where(inside, tmpl_deps[trow], 0)
+        step_kind[row] = kind
+        children_todo[row] = torch.where(inside, todo, 0)
+        max_parallel[row] = torch.where(inside, tmpl_maxp[trow], 0)
+        children_out[row] = 0
+        children_done[row] = 0
+        children_fail[row] = 0
+        children_emitted[row] = 0
+        next_ready[row] = torch.where(inside, tick1 + tmpl_delay[trow], 0)
+        dispatch_tick[row] = torch.where(inside, tick1, 0)
+        n_steps[slot] = ns
+        cond_bits[slot] = int(req_cond[i])
+        run_state[slot] = 0
+        run_active[slot] = 1
+        run_life[slot] = WFL_LIVE
+        run_gen[slot] += 1
+        out_slot[i] = slot
+        out_gen[i] = int(run_gen[slot])
+
+
+def wf_cancel_ref(req_slot, req_gen, run_life, run_gen, run_active, run_state,
+                  n_steps, step_state, cancel_count, out_ok):
+    NR = int(n_steps.shape[0])
+    for i in range(int(req_slot.shape[0])):
+        slot = int(req_slot[i])
+        ok = (0 <= slot < NR and int(run_life[slot]) == WFL_LIVE
+              and int(run_gen[slot]) == int(req_gen[i])
+              and int(run_active[slot]) == 1)
+        if not ok:
+            out_ok[i] = 0
+            continue
+        for s in range(int(n_steps[slot])):
+            ri = slot * 64 + s
+            if int(step_state[ri]) in (WFS_PENDING, WFS_DISPATCHED, WFS_WAITING):
+                step_state[ri] = WFS_CANCELLED
+        run_active[slot] = 0
+        run_state[slot] = WFS_CANCELLED
+        out_ok[i] = 1
+        cancel_count[0] += 1
+
+
+def wf_retire_ref(run_life, run_active, run_state, run_gen, n_steps,
+                  children_out, dispatch_tick, tick, cutoff: int,
+                  done_slot, done_gen, done_state, done_count):
+    NR = int(n_steps.shape[0])
+    cap = int(done_slot.shape[0])
+    stale = int(tick[0]) - cutoff
+    for run in range(NR):
+        life = int(run_life[run])
+        if life == WFL_LIVE and int(run_active[run]) == 0:
+            pos = int(done_count[0])
+            done_count[0] = pos + 1
+            if pos < cap:
+                done_slot[pos] = run
+                done_gen[pos] = int(run_gen[run])
+                done_state[pos] = int(run_state[run])
+            life = WFL_DRAINING
+        if life != WFL_DRAINING:
+            continue
+        # quiescent: no step has a child out that can still apply
+        quiet = all(
+            int(children_out[run * 64 + s]) <= 0
+            or int(dispatch_tick[run * 64 + s]) <= stale
+            for s in range(int(n_steps[run])))
+        life = WFL_FREE if quiet else WFL_DRAINING
+        if life != int(run_life[run]):
+            run_life[run] = life

@@ -29,6 +29,14 @@ Step kinds: WORKER (one child job), FOR_EACH (fanout children, per-child
 retry), APPROVAL (host-granted), CONDITION (pre-evaluated bit ->
 SUCCEEDED/SKIPPED), DELAY (tick gate). Dependencies are 64-bit step masks;
 SKIPPED satisfies a dependency, FAILED permanently blocks (the run fails).
+
+Static mode (the default) creates every run at construction and re-enters
+them by reset_runs() / wf_readmit. Dynamic mode (`dynamic_capacity=NR`)
+starts with NR FREE slots and gives runs a lifecycle between ticks:
+admit() (wf_admit, lowest free slots, templates held on the device),
+cancel() (wf_cancel, checked against the slot's generation) and
+drain_completed() (wf_retire: completion records, and release of slots
+whose rows are quiescent). The tick body is the same in both modes.
 """
 from __future__ import annotations
 
@@ -44,6 +52,8 @@ from .pipeline import _RefOps
 
 WFS_PENDING, WFS_DISPATCHED, WFS_WAITING = 0, 1, 2
 WFS_SUCCEEDED, WFS_FAILED, WFS_SKIPPED = 3, 4, 5
+WFS_CANCELLED = 6            # dynamic mode: cancelled run / step
+WFL_FREE, WFL_LIVE, WFL_DRAINING = 0, 1, 2   # life of a run slot
 WFK_WORKER, WFK_FOR_EACH, WFK_APPROVAL, WFK_CONDITION, WFK_DELAY = 0, 1, 2, 3, 4
 
 
@@ -106,6 +116,10 @@ class WorkflowPipeline:
         pad_cap: Optional[int] = None,
         replicate: Optional[int] = None,
         seed: int = 7,
+        # dynamic mode: `dags` are templates, the table has this many run
+        # slots, all FREE; runs enter through admit() (see "run lifecycle")
+        dynamic_capacity: Optional[int] = None,
+        template_cap: int = 256,
     ):
         device = torch.device(device)
         self.ext = _RefOps() if backend == "ref" else get_ext(required=True)
@@ -122,6 +136,12 @@ class WorkflowPipeline:
         if replicate is not None:
             assert len(dags) == 1
         NR = replicate if replicate is not None else len(dags)
+        self.dynamic = dynamic_capacity is not None
+        if self.dynamic:
+            assert replicate is None, "dynamic mode admits runs, it replicates none"
+            NR = int(dynamic_capacity)
+            assert NR >= 1 and len(dags) <= template_cap
+            templates, dags = list(dags), ()   # no run exists at construction
         self.NR = NR
         assert all(len(d.steps) <= 64 for d in dags), "device DAGs cap at 64 steps"
 
@@ -168,6 +188,12 @@ class WorkflowPipeline:
             nsteps = nsteps.repeat(NR)
             cond = cond.repeat(NR)
             total_children *= NR
+        if self.dynamic:
+            # arena sizing only: every slot holding the widest template
+            total_children = NR * max(
+                [sum(s.fanout if s.kind == WFK_FOR_EACH else 1 for s in t.steps
+                     if s.kind in (WFK_FOR_EACH, WFK_WORKER)) for t in templates],
+                default=1)
         self.total_children = total_children
         self._tmpl = {
             "step_state": st, "deps_mask": deps, "step_kind": kinds,
@@ -305,12 +331,221 @@ class WorkflowPipeline:
             self._appr_h_count = None
 
         self._tick = 0
+        if self.dynamic:
+            self._init_dynamic(templates, template_cap)
+
+    # ---- run lifecycle (dynamic mode) ---------------------------------------
+    def _init_dynamic(self, templates: Sequence[DagSpec], template_cap: int) -> None:
+        d, NR, TC = self.device, self.NR, int(template_cap)
+        self.run_active.zero_()               # every slot starts FREE
+        self.template_cap = TC
+        self.n_templates = 0
+        self._tmpl_cond: List[int] = []
+        self.tmpl_deps = torch.zeros(TC * 64, dtype=torch.int64, device=d)
+        self.tmpl_kind = torch.zeros(TC * 64, dtype=torch.uint8, device=d)
+        self.tmpl_todo = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+        self.tmpl_maxp = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+        self.tmpl_delay = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+        self.tmpl_nsteps = torch.zeros(TC, dtype=torch.uint8, device=d)
+        self.run_life = torch.zeros(NR, dtype=torch.uint8, device=d)
+        self.run_gen = torch.zeros(NR, dtype=torch.int32, device=d)
+        self.cancel_count = torch.zeros(1, dtype=torch.int64, device=d)
+        # completion records share one buffer so a drain is one D2H copy:
+        # [count | slot[NR] | gen[NR] | state[NR]]. A run is reported once,
+        # so NR records cannot overflow.
+        self._done_buf = torch.zeros(1 + 3 * NR, dtype=torch.int32, device=d)
+        self.done_count = self._done_buf[0:1]
+        self.done_slot = self._done_buf[1:1 + NR]
+        self.done_gen = self._done_buf[1 + NR:1 + 2 * NR]
+        self.done_state = self._done_buf[1 + 2 * NR:1 + 3 * NR]
+        self._done_host = torch.zeros(1 + 3 * NR, dtype=torch.int32)
+        if d.type == "cuda":
+            self._done_host = self._done_host.pin_memory()
+        # wf_admit workspaces: free-slot masks and scanned block counts
+        nblk = (NR + 255) // 256
+        self._free_mask = torch.zeros(nblk * 4, dtype=torch.int64, device=d)
+        self._blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
+        for dag in templates:
+            self.add_template(dag)
+        self._capture_dynamic()
+
+    def _require_dynamic(self, dynamic: bool, what: str) -> None:
+        if self.dynamic != dynamic:
+            raise RuntimeError(
+                f"{what} needs a {'dynamic' if dynamic else 'static'}-mode "
+                f"pipeline (dynamic_capacity {'unset' if dynamic else 'set'})")
+
+    def add_template(self, dag: DagSpec) -> int:
+        """Register one more workflow template; returns its id."""
+        self._require_dynamic(True, "add_template")
+        if len(dag.steps) > 64:
+            raise ValueError("device DAGs cap at 64 steps")
+        t = self.n_templates
+        if t >= self.template_cap:
+            raise ValueError(f"template table full ({self.template_cap})")
+        for spec in dag.steps:
+            if spec.kind == WFK_FOR_EACH and spec.fanout > self.CB:
+                raise ValueError(f"fanout {spec.fanout} can never be emitted "
+                                 f"(child arena {self.CB})")
+        deps = torch.zeros(64, dtype=torch.int64)
+        kinds = torch.zeros(64, dtype=torch.uint8)
+        todo = torch.zeros(64, dtype=torch.int32)
+        maxp = torch.zeros(64, dtype=torch.int32)
+        delay = torch.zeros(64, dtype=torch.int32)
+        cbits = 0
+        for s, spec in enumerate(dag.steps):
+            kinds[s] = spec.kind
+            m = 0
+            for dep in spec.deps:
+                m |= 1 << dep
+            deps[s] = m - (1 << 64) if m >= (1 << 63) else m
+            if spec.kind == WFK_FOR_EACH:
+                todo[s] = spec.fanout
+            elif spec.kind == WFK_WORKER:
+                todo[s] = 1
+            if spec.kind == WFK_DELAY:
+                delay[s] = spec.delay_ticks
+            maxp[s] = spec.max_parallel
+            if spec.cond:
+                cbits |= 1 << s
+        row = slice(t * 64, t * 64 + 64)
+        self.tmpl_deps[row].copy_(deps)
+        self.tmpl_kind[row].copy_(kinds)
+        self.tmpl_todo[row].copy_(todo)
+        self.tmpl_maxp[row].copy_(maxp)
+        self.tmpl_delay[row].copy_(delay)
+        self.tmpl_nsteps[t:t + 1].fill_(len(dag.steps))
+        self._tmpl_cond.append(cbits - (1 << 64) if cbits >= (1 << 63) else cbits)
+        self.n_templates = t + 1
+        return t
+
+    def admit(self, templates: Sequence[int], cond_bits=None, fanout=None):
+        """Admit one run per template id into the lowest FREE slots; returns
+        (slots, gens). slots[i] == -1: the table was full for request i."""
+        self._require_dynamic(True, "admit")
+        tl = [int(t) for t in templates]
+        n = len(tl)
+        for t in tl:
+            if not 0 <= t < self.n_templates:
+                raise ValueError(f"unregistered template id {t}")
+        fl = [0] * n if fanout is None else [int(f) for f in fanout]
+        for f in fl:
+            if f < 0 or f > self.CB:
+                raise ValueError(
+                    f"fanout {f} can never be emitted (child arena {self.CB})")
+        if cond_bits is None:
+            cl = [self._tmpl_cond[t] for t in tl]
+        else:
+            cl = [int(c) - (1 << 64) if int(c) >= (1 << 63) else int(c)
+                  for c in cond_bits]
+        if len(fl) != n or len(cl) != n:
+            raise ValueError("cond_bits / fanout must match templates in length")
+        if n == 0:
+            return [], []
+        # one H2D: [cond as int64 | template ids | fanouts] in one buffer
+        req = torch.empty(4 * n, dtype=torch.int32)
+        req[:2 * n].view(torch.int64).copy_(torch.tensor(cl, dtype=torch.int64))
+        req[2 * n:3 * n] = torch.tensor(tl, dtype=torch.int32)
+        req[3 * n:] = torch.tensor(fl, dtype=torch.int32)
+        req = req.to(self.device)
+        out = torch.empty(2 * n, dtype=torch.int32, device=self.device)
+        self.ext.wf_admit(
+            req[2 * n:3 * n], req[:2 * n].view(torch.int64), req[3 * n:],
+            self.tmpl_deps, self.tmpl_kind, self.tmpl_todo, self.tmpl_maxp,
+            self.tmpl_delay, self.tmpl_nsteps,
+            self.step_state, self.step_attempts, self.deps_mask, self.step_kind,
+            self.children_todo, self.max_parallel, self.children_out,
+            self.children_done, self.children_fail, self.children_emitted,
+            self.next_ready, self.dispatch_tick, self.n_steps, self.cond_bits,
+            self.run_state, self.run_active, self.run_life, self.run_gen,
+            self.tick_buf, self._free_mask, self._blk_scan,
+            out[:n], out[n:], self.admit_count)
+        h = out.cpu()
+        return h[:n].tolist(), h[n:].tolist()
+
+    def cancel(self, slots: Sequence[int], gens: Sequence[int]) -> List[int]:
+        """Cancel the runs named by (slot, gen) handles; returns 1 per request
+        that took effect. A stale generation, a finished run or a repeated
+        slot in the same call gives 0."""
+        self._require_dynamic(True, "cancel")
+        sl, gl = [int(s) for s in slots], [int(g) for g in gens]
+        if len(sl) != len(gl):
+            raise ValueError("slots and gens must match in length")
+        first = {}
+        for i, s in enumerate(sl):   # the kernel assumes distinct slots
+            first.setdefault(s, i)
+        keep = sorted(first.values())
+        ok = [0] * len(sl)
+        if not keep:
+            return ok
+        n = len(keep)
+        req = torch.tensor([sl[i] for i in keep] + [gl[i] for i in keep],
+                           dtype=torch.int32).to(self.device)
+        out = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self.ext.wf_cancel(req[:n], req[n:], self.run_life, self.run_gen,
+                           self.run_active, self.run_state, self.n_steps,
+                           self.step_state, self.cancel_count, out)
+        for i, v in zip(keep, out.cpu().tolist()):
+            ok[i] = v
+        return ok
+
+    def drain_completed(self):
+        """Report every run that became terminal since the last drain, once,
+        as (slots, gens, states) sorted by slot, and free the slots whose
+        rows are quiescent."""
+        self._require_dynamic(True, "drain_completed")
+        self.done_count.zero_()
+        self.ext.wf_retire(self.run_life, self.run_active, self.run_state,
+                           self.run_gen, self.n_steps, self.children_out,
+                           self.dispatch_tick, self.tick_buf, self.timeout_cutoff,
+                           self.done_slot, self.done_gen, self.done_state,
+                           self.done_count)
+        h = self._done_host
+        h.copy_(self._done_buf)      # the one D2H (synchronising)
+        NR = self.NR
+        n = min(int(h[0]), NR)
+        rec = sorted(zip(h[1:1 + n].tolist(), h[1 + NR:1 + NR + n].tolist(),
+                         h[1 + 2 * NR:1 + 2 * NR + n].tolist()))
+        return [r[0] for r in rec], [r[1] for r in rec], [r[2] for r in rec]
+
+    def _capture_dynamic(self) -> None:
+        """Dynamic mode warms up and captures the tick on the EMPTY table, at
+        construction: n calls of tick() then advance the tables by exactly n
+        ticks with the graph or without it. On an empty table the body
+        changes only the tick counter and (never, but restored alike) the
+        cumulative counters, which are put back."""
+        import os
+
+        if self.device.type != "cuda" or self.world > 1 \
+                or os.environ.get("CORDUM_WF_NO_GRAPH"):
+            return
+        saved = [(t, t.clone()) for t in
+                 (self.tick_buf, self.wf_counts, self.timeout_count,
+                  self.retry_count, self.admit_count, self.rq_dead)]
+        for _ in range(2):
+            self._tick_device_body()
+        torch.cuda.synchronize(self.device)
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._tick_device_body()
+            self._wf_graph = g
+        except Exception as e:
+            import sys
+
+            print(f"[cordum] wf-graph capture failed, running eager: {e!r}",
+                  file=sys.stderr)
+            self._wf_graph = ()
+        for t, v in saved:
+            t.copy_(v)
+        torch.cuda.synchronize(self.device)
 
     # ---- run admission -------------------------------------------------------
     def reset_runs(self) -> None:
         """Re-admit the whole run wave: copy the creation image back into the
         device tables (this is the honest run-creation H2D cost when the
         template lives on the host; templates are staged once)."""
+        self._require_dynamic(False, "reset_runs")
         if not hasattr(self, "_tmpl_dev"):
             self._tmpl_dev = {k: v.to(self.device) for k, v in self._tmpl.items()}
         t = self._tmpl_dev
@@ -534,7 +769,9 @@ class WorkflowPipeline:
             ext.wf_grant(runs.to(self.device), steps.to(self.device), v, n,
                          self.step_state)
 
-        if self.device.type == "cuda" and self.world == 1 and self._ensure_wf_graph():
+        # dynamic mode captured at construction, on the empty table
+        if self.device.type == "cuda" and self.world == 1 and (
+                bool(self._wf_graph) if self.dynamic else self._ensure_wf_graph()):
             self._wf_graph.replay()
         else:
             self._tick_device_body()
@@ -568,6 +805,7 @@ class WorkflowPipeline:
     def readmit_succeeded(self) -> None:
         """Terminal SUCCEEDED runs re-enter from the creation template so the
         table stays full (config #5 'hold 1M concurrent runs')."""
+        self._require_dynamic(False, "readmit_succeeded")
         t = self._ensure_tmpl_dev()
         self.ext.wf_readmit(self.run_active, self.run_state, self.n_steps,
                             self.step_state, self.step_attempts,
@@ -582,6 +820,7 @@ class WorkflowPipeline:
         then re-admit those rows through the same template reset. Returns
         the number drained; the caller's DLQ bookkeeping must reconcile
         exactly with the device failed counter at the end of a soak."""
+        self._require_dynamic(False, "drain_failed_to_dlq")
         failed = (self.run_state == WFS_FAILED) & (self.run_active == 0)
         ids = torch.nonzero(failed).flatten()
         n = int(ids.numel())
@@ -617,6 +856,7 @@ class WorkflowPipeline:
 
     def run_wave(self, max_ticks: int = 256) -> WfStats:
         """Admit the full run wave and tick until every run is terminal."""
+        self._require_dynamic(False, "run_wave")
         t0 = time.perf_counter()
         self.reset_runs()
         start_ok, start_fail = self.counts()
