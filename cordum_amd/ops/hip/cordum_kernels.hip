@@ -1348,6 +1348,102 @@ __global__ __launch_bounds__(BLOCK) void wf_retire_kernel(
     }
 }
 
+// step-transition journal: an observer of the tables above. It compares
+// every step state of the LIVE and DRAINING rows with the state it last
+// reported (ev_shadow_state) and appends one 16-byte record per difference:
+//   word0 slot | word1 gen | word2 step | from<<8 | to<<16 | word3 2*tick+phase
+// A row whose generation differs from ev_shadow_gen was admitted since its
+// shadow was written: its shadow counts as all PENDING, the image wf_admit
+// writes, and the admission itself is no event. FREE rows cost their life
+// byte only.
+//
+// Layout: 4 lanes per row, 16 steps (one 16-byte load of the states and one
+// of the shadow) per lane, 16 rows per wave, 64 rows per block. A wave with
+// no difference and no generation change leaves after the loads. Otherwise
+// it reserves list space with one atomic for the whole wave (per-lane counts,
+// wave prefix sum); a record at a position >= cap is not written and its
+// shadow byte does not advance, so the next pass finds the change again: a
+// full list delays and coalesces events, it loses none.
+//
+// ev_count: a wave adds to it only if it read it below cap, and adds at most
+// 1024 (16 rows x 64 steps). Every wave of a pass can do that once, so
+//   ev_count <= max(cap - 1, value at entry) + 64 * NR
+// however many passes run before the host drains it. The host binding
+// rejects tables for which that could wrap.
+__global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
+    const unsigned char* __restrict__ step_state,   // [NR*64]
+    const unsigned char* __restrict__ run_life,     // [NR]
+    const int* __restrict__ run_gen,                // [NR]
+    const int* __restrict__ tick_p, int phase,
+    unsigned char* __restrict__ ev_shadow_state,    // [NR*64]
+    int* __restrict__ ev_shadow_gen,                // [NR]
+    int* __restrict__ ev_rec,                       // [cap*4]
+    int* __restrict__ ev_count,                     // [1]
+    int NR, int cap)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int lane = threadIdx.x % WAVE;
+    const int r = t >> 2;                           // 4 lanes per row
+    const int q = t & 3;                            // steps 16q .. 16q+15
+    const bool live = r < NR && run_life[r] != WFL_FREE;
+    const size_t off = (size_t)r * 64 + (size_t)q * 16;
+    int gen = 0;
+    bool regen = false;
+    uint4 st = make_uint4(0u, 0u, 0u, 0u), sh = st; // WFS_PENDING == 0
+    if (live) {
+        gen = run_gen[r];
+        regen = gen != ev_shadow_gen[r];
+        st = *reinterpret_cast<const uint4*>(step_state + off);
+        if (!regen) sh = *reinterpret_cast<const uint4*>(ev_shadow_state + off);
+    }
+    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
+    const unsigned hw[4] = {sh.x, sh.y, sh.z, sh.w};
+    unsigned diff = 0u;                             // bit j: step 16q+j differs
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        diff |= (unsigned)((((sw[j >> 2] ^ hw[j >> 2]) >> ((j & 3) * 8)) & 0xffu) != 0u) << j;
+    const int n = __popc(diff);
+    if (!__any(n > 0 || regen)) return;             // wave-uniform early exit
+
+    int incl = n;                                   // inclusive wave prefix sum
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int v = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += v;
+    }
+    const int total = __shfl(incl, WAVE - 1, WAVE);
+    int base = 0;
+    if (lane == 0 && total > 0) {
+        const int seen = __hip_atomic_load(ev_count, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+        base = seen >= cap ? cap : atomicAdd(ev_count, total);
+    }
+    base = __shfl(base, 0, WAVE);
+    int pos = base + incl - n;
+    const int stamp = 2 * *tick_p + phase;
+    unsigned nw[4] = {hw[0], hw[1], hw[2], hw[3]};  // the shadow after this pass
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if ((diff >> j) & 1u) {
+            if (pos < cap) {
+                const int sft = (j & 3) * 8;
+                const unsigned from = (hw[j >> 2] >> sft) & 0xffu;
+                const unsigned to = (sw[j >> 2] >> sft) & 0xffu;
+                *reinterpret_cast<int4*>(ev_rec + (size_t)pos * 4) = make_int4(
+                    r, gen, (int)((unsigned)(q * 16 + j) | from << 8 | to << 16), stamp);
+                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | (to << sft);
+            }
+            ++pos;
+        }
+    }
+    // a re-admitted row's stale shadow is replaced whole; otherwise the
+    // shadow is written only where an event advanced it
+    if (regen || nw[0] != hw[0] || nw[1] != hw[1] || nw[2] != hw[2] || nw[3] != hw[3])
+        *reinterpret_cast<uint4*>(ev_shadow_state + off) =
+            make_uint4(nw[0], nw[1], nw[2], nw[3]);
+    if (regen && q == 0) ev_shadow_gen[r] = gen;
+}
+
 // ---------------------------------------------------------------------------
 // K4: deadline / staleness scan -> TIMEOUT candidates (compacted list)
 // ---------------------------------------------------------------------------
@@ -3062,6 +3158,37 @@ void wf_retire(torch::Tensor run_life, torch::Tensor run_active, torch::Tensor r
         done_state.data_ptr<int>(), done_count.data_ptr<int>(), NR, cap);
 }
 
+// one journal pass on the current stream; cap is ev_rec's length in records
+void wf_journal(torch::Tensor step_state, torch::Tensor run_life, torch::Tensor run_gen,
+                torch::Tensor tick, int64_t phase,
+                torch::Tensor ev_shadow_state, torch::Tensor ev_shadow_gen,
+                torch::Tensor ev_rec, torch::Tensor ev_count)
+{
+    const int64_t NR = run_life.numel();
+    const int64_t cap = ev_rec.numel() / 4;
+    if (NR <= 0) return;
+    TORCH_CHECK(step_state.numel() == NR * 64 && ev_shadow_state.numel() == NR * 64
+                && run_gen.numel() == NR && ev_shadow_gen.numel() == NR,
+                "wf_journal: table sizes disagree");
+    TORCH_CHECK(cap >= 1 && ev_rec.numel() == cap * 4 && ev_count.numel() >= 1
+                && tick.numel() >= 1, "wf_journal: event list needs cap*4 words, cap >= 1");
+    TORCH_CHECK(step_state.is_contiguous() && ev_shadow_state.is_contiguous()
+                && ev_rec.is_contiguous(), "wf_journal: tables must be contiguous");
+    // the counter's bound (see the kernel) and the 4-lanes-per-row grid in int
+    TORCH_CHECK(cap + 64 * NR + 1024 <= (int64_t)INT_MAX,
+                "wf_journal: cap + 64*NR would let the event counter wrap");
+    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
+                && (uintptr_t)ev_shadow_state.data_ptr<uint8_t>() % 16 == 0
+                && (uintptr_t)ev_rec.data_ptr<int>() % 16 == 0,
+                "wf_journal: states, shadow and records must be 16-byte aligned");
+    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(wf_journal_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        step_state.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
+        run_gen.data_ptr<int>(), tick.data_ptr<int>(), (int)phase,
+        ev_shadow_state.data_ptr<uint8_t>(), ev_shadow_gen.data_ptr<int>(),
+        ev_rec.data_ptr<int>(), ev_count.data_ptr<int>(), (int)NR, (int)cap);
+}
+
 void materialize_rq_payload(torch::Tensor payload, torch::Tensor rq_prev_payload,
                             torch::Tensor rq_src, torch::Tensor rq_count,
                             torch::Tensor rq_payload, int64_t stride)
@@ -3348,6 +3475,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_admit", &wf_admit, "K3-WF run admission into the lowest free slots");
     m.def("wf_cancel", &wf_cancel, "K3-WF generation-checked run cancellation");
     m.def("wf_retire", &wf_retire, "K3-WF completion records + quiescent slot release");
+    m.def("wf_journal", &wf_journal, "K3-WF step-transition journal pass (observer)");
     m.def("materialize_rq_payload", &materialize_rq_payload, "copy requeued payload rows into the rq arena");
     m.def("gather_payload_padded", &gather_payload_padded, "payload gather into padded send arena");
     m.def("echo_padded", &echo_padded, "region-valid echo over padded recv arena");

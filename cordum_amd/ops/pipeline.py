@@ -344,6 +344,11 @@ class _RefOps:
 
         wf_retire_ref(rl, ra, rs, rg, ns, co, dt, tick, int(cutoff), ds, dg, dst, dc)
 
+    def wf_journal(self, st, rl, rg, tick, phase, shs, shg, rec, cnt):
+        from .reference import wf_journal_ref
+
+        wf_journal_ref(st, rl, rg, tick, int(phase), shs, shg, rec, cnt)
+
     def materialize_rq_payload(self, payload, prev_payload, rq_src, rq_count,
                                rq_payload, stride):
         from .reference import materialize_rq_payload_ref

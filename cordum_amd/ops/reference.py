@@ -670,3 +670,35 @@ def wf_retire_ref(run_life, run_active, run_state, run_gen, n_steps,
         life = WFL_FREE if quiet else WFL_DRAINING
         if life != int(run_life[run]):
             run_life[run] = life
+
+
+def wf_journal_ref(step_state, run_life, run_gen, tick, phase: int,
+                   ev_shadow_state, ev_shadow_gen, ev_rec, ev_count):
+    """One pass of the step-transition journal. Rows and steps are visited in
+    ascending order, so a full list keeps the lowest (slot, step) changes; a
+    change that does not fit leaves its shadow byte where it was (PENDING
+    after a generation change) and is found again by the next pass. The
+    count stops at cap: nothing is added once it is at or above it."""
+    NR = int(run_life.shape[0])
+    cap = int(ev_rec.shape[0]) // 4
+    stamp = 2 * int(tick[0]) + int(phase)
+    live = run_life[:NR] != WFL_FREE
+    regen = live & (run_gen[:NR] != ev_shadow_gen[:NR])
+    st = step_state.view(NR, 64)
+    sh = ev_shadow_state.view(NR, 64)
+    sh[regen] = WFS_PENDING
+    ev_shadow_gen[regen] = run_gen[:NR][regen]
+    idx = torch.nonzero((st != sh) & live[:, None])      # ascending (row, step)
+    count = int(ev_count[0])
+    k = min(int(idx.shape[0]), max(0, cap - count))
+    if k == 0:
+        return
+    rows, steps = idx[:k, 0], idx[:k, 1]
+    frm, to = sh[rows, steps].to(torch.int32), st[rows, steps].to(torch.int32)
+    rec = ev_rec.view(-1, 4)[count:count + k]
+    rec[:, 0] = rows.to(torch.int32)
+    rec[:, 1] = run_gen[:NR][rows]
+    rec[:, 2] = steps.to(torch.int32) | (frm << 8) | (to << 16)
+    rec[:, 3] = stamp
+    sh[rows, steps] = st[rows, steps]
+    ev_count[0] = count + k

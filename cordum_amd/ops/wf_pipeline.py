@@ -37,6 +37,12 @@ admit() (wf_admit, lowest free slots, templates held on the device),
 cancel() (wf_cancel, checked against the slot's generation) and
 drain_completed() (wf_retire: completion records, and release of slots
 whose rows are quiescent). The tick body is the same in both modes.
+
+With `event_cap=N` dynamic mode also keeps a step-transition journal: one
+more kernel (wf_journal) ends the tick and appends a record per step whose
+state changed since it last looked, and drain_events() returns them (see
+"step-transition journal" below). Without it nothing is allocated and the
+tick launches exactly the sequence above.
 """
 from __future__ import annotations
 
@@ -120,7 +126,19 @@ class WorkflowPipeline:
         # slots, all FREE; runs enter through admit() (see "run lifecycle")
         dynamic_capacity: Optional[int] = None,
         template_cap: int = 256,
+        # dynamic mode only: journal every step transition into a device list
+        # of this many records (see "step-transition journal")
+        event_cap: Optional[int] = None,
     ):
+        if event_cap is not None:
+            if dynamic_capacity is None:
+                raise ValueError("event_cap needs dynamic_capacity: the journal "
+                                 "reports runs by (slot, generation)")
+            if int(event_cap) < 1:
+                raise ValueError("event_cap must be >= 1")
+            event_cap = int(event_cap)
+        self.event_cap = event_cap
+        self.event_overflows = 0
         device = torch.device(device)
         self.ext = _RefOps() if backend == "ref" else get_ext(required=True)
         self.device = device
@@ -365,6 +383,20 @@ class WorkflowPipeline:
         nblk = (NR + 255) // 256
         self._free_mask = torch.zeros(nblk * 4, dtype=torch.int64, device=d)
         self._blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
+        if self.event_cap is not None:
+            # journal tables. The list is one buffer, [count, pad x3 | records],
+            # so the records start 16-byte aligned for the kernel's vector
+            # stores. The shadow starts as what an empty table is: all PENDING
+            # at generation 0, which no admitted run ever has.
+            if self.event_cap + 64 * NR + 1024 > (1 << 31) - 1:
+                raise ValueError("event_cap + 64 * dynamic_capacity must stay "
+                                 "below 2^31 (the device event counter)")
+            self.ev_shadow_state = torch.zeros(NR * 64, dtype=torch.uint8, device=d)
+            self.ev_shadow_gen = torch.zeros(NR, dtype=torch.int32, device=d)
+            self._ev_buf = torch.zeros(4 + 4 * self.event_cap, dtype=torch.int32,
+                                       device=d)
+            self.ev_count = self._ev_buf[0:1]
+            self.ev_rec = self._ev_buf[4:]
         for dag in templates:
             self.add_template(dag)
         self._capture_dynamic()
@@ -485,6 +517,10 @@ class WorkflowPipeline:
         self.ext.wf_cancel(req[:n], req[n:], self.run_life, self.run_gen,
                            self.run_active, self.run_state, self.n_steps,
                            self.step_state, self.cancel_count, out)
+        if self.event_cap is not None:
+            # the slot can be drained and re-admitted before the next tick:
+            # its CANCELLED transitions are journaled now or never
+            self._journal(1)
         for i, v in zip(keep, out.cpu().tolist()):
             ok[i] = v
         return ok
@@ -508,6 +544,70 @@ class WorkflowPipeline:
                          h[1 + 2 * NR:1 + 2 * NR + n].tolist()))
         return [r[0] for r in rec], [r[1] for r in rec], [r[2] for r in rec]
 
+    # ---- step-transition journal (dynamic mode, event_cap set) ---------------
+    # wf_journal compares every step state of the LIVE and DRAINING rows with
+    # the state it last reported and appends (slot, gen, step, from, to,
+    # stamp) per difference; stamp = 2 * tick + phase. Phase 0 is the pass
+    # that ends each tick (inside the captured graph), phase 1 a pass between
+    # ticks (after cancel(), and the catch-up passes of drain_events()).
+    #
+    # Order contract of drain_events():
+    # - within one returned list a step never has two events with the same
+    #   stamp, and list order is time order;
+    # - per (slot, gen, step) the events chain: the first `from` is PENDING,
+    #   each `from` is the previous `to`, and after a drain the last `to` is
+    #   the live step_state;
+    # - transitions between two passes coalesce: a worker step dispatched and
+    #   completed in the same tick is one event, PENDING -> SUCCEEDED;
+    # - the stamp's tick is the tick of detection. A full list delays events
+    #   (to a later pass, with that pass's stamp) and loses none, provided
+    #   the list is drained before the run's slot is released: a FREE row is
+    #   not journaled, so drain events before drain_completed().
+    def _require_events(self, what: str) -> None:
+        self._require_dynamic(True, what)
+        if self.event_cap is None:
+            raise RuntimeError(f"{what} needs the step journal (event_cap unset)")
+
+    def _journal(self, phase: int) -> None:
+        self.ext.wf_journal(self.step_state, self.run_life, self.run_gen,
+                            self.tick_buf, phase, self.ev_shadow_state,
+                            self.ev_shadow_gen, self.ev_rec, self.ev_count)
+
+    def drain_events(self):
+        """Every step transition journaled since the last drain, as (slots,
+        gens, steps, from_states, to_states, stamps) in time order: sorted by
+        (stamp, slot, step). If the device list had filled up, catch-up
+        passes run and are drained until one fits, their sub-lists appended
+        in that order; each such pass either finishes or emits event_cap
+        events, so this ends. `event_overflows` counts the drains that
+        needed one."""
+        self._require_events("drain_events")
+        cap = self.event_cap
+        cols: List[List[int]] = [[], [], [], [], [], []]
+        overflowed = False
+        while True:
+            n = int(self.ev_count.cpu()[0])          # synchronising
+            m = min(n, cap)
+            if n:
+                self.ev_count.zero_()
+            if m:
+                rec = self._ev_buf[4:4 + 4 * m].cpu().view(m, 4).to(torch.int64)
+                w2 = rec[:, 2]
+                step = w2 & 0xFF
+                order = torch.sort(rec[:, 0] * 64 + step, stable=True)[1]
+                order = order[torch.sort(rec[order, 3], stable=True)[1]]
+                rec, w2, step = rec[order], w2[order], step[order]
+                for c, v in zip(cols, (rec[:, 0], rec[:, 1], step, (w2 >> 8) & 0xFF,
+                                       (w2 >> 16) & 0xFF, rec[:, 3])):
+                    c.extend(v.tolist())
+            # a list left full may have turned changes away: look again
+            if n < cap:
+                break
+            overflowed = True
+            self._journal(1)
+        self.event_overflows += int(overflowed)
+        return tuple(cols)
+
     def _capture_dynamic(self) -> None:
         """Dynamic mode warms up and captures the tick on the EMPTY table, at
         construction: n calls of tick() then advance the tables by exactly n
@@ -519,9 +619,11 @@ class WorkflowPipeline:
         if self.device.type != "cuda" or self.world > 1 \
                 or os.environ.get("CORDUM_WF_NO_GRAPH"):
             return
-        saved = [(t, t.clone()) for t in
-                 (self.tick_buf, self.wf_counts, self.timeout_count,
-                  self.retry_count, self.admit_count, self.rq_dead)]
+        counters = [self.tick_buf, self.wf_counts, self.timeout_count,
+                    self.retry_count, self.admit_count, self.rq_dead]
+        if self.event_cap is not None:
+            counters.append(self.ev_count)
+        saved = [(t, t.clone()) for t in counters]
         for _ in range(2):
             self._tick_device_body()
         torch.cuda.synchronize(self.device)
@@ -698,6 +800,8 @@ class WorkflowPipeline:
                       self.next_ready, self.tick_buf, self.max_retries, self.retry_count)
         ext.wf_status(self.step_state, self.n_steps, self.run_active,
                       self.run_state, self.wf_counts)
+        if self.event_cap is not None:
+            self._journal(0)
         if self._appr_h_count is not None:
             # stream-ordered async D2H of the approval count into pinned
             # memory: the host polls it with event.query() instead of a

@@ -8,34 +8,110 @@ run id, and turns the device's completion records into `(run_id, status)`
 pairs. `dag_from_workflow` lowers a `Workflow` to the `DagSpec` the device
 runs, or says (None) that the workflow must stay on the host engine.
 
-Wiring an API route to this table, and result / timeline / output
-materialisation, are not done here.
+With the pipeline's step journal on (`event_cap`), the table also turns the
+device's step-transition records into `StepEvent`s keyed by run id, per-step
+`STEP_*` statuses, and, given a `WorkflowStore`, the timeline events and run
+records the API serves.
+
+Wiring an API route to this table, and result / output materialisation, are
+not done here.
 """
 from __future__ import annotations
 
 import math
 from collections import deque
-from typing import Any, Deque, Dict, List, Optional, Tuple
+from typing import Any, Deque, Dict, List, NamedTuple, Optional, Tuple, Union
 
 from ..ops.wf_pipeline import (
     DagSpec,
     StepSpec,
     WFK_APPROVAL,
+    WFK_CONDITION,
     WFK_DELAY,
     WFK_FOR_EACH,
     WFK_WORKER,
     WFS_CANCELLED,
+    WFS_DISPATCHED,
     WFS_FAILED,
+    WFS_PENDING,
+    WFS_SKIPPED,
     WFS_SUCCEEDED,
+    WFS_WAITING,
     WorkflowPipeline,
 )
-from .models import RUN_CANCELLED, RUN_FAILED, RUN_SUCCEEDED, Step
+from ..utils.clock import SYSTEM_CLOCK
+from .models import (
+    RUN_CANCELLED,
+    RUN_FAILED,
+    RUN_SUCCEEDED,
+    STEP_CANCELLED,
+    STEP_FAILED,
+    STEP_PENDING,
+    STEP_RUNNING,
+    STEP_SUCCEEDED,
+    STEP_WAITING,
+    Step,
+    StepRun,
+    TimelineEvent,
+)
 
 _STATUS = {
     WFS_SUCCEEDED: RUN_SUCCEEDED,
     WFS_FAILED: RUN_FAILED,
     WFS_CANCELLED: RUN_CANCELLED,
 }
+
+# device step state -> the status the API shows. A false condition is
+# SKIPPED on the device; the host engine completes it as succeeded with the
+# value False (workflow/engine.py, the condition step).
+_STEP_STATUS = {
+    WFS_PENDING: STEP_PENDING,
+    WFS_DISPATCHED: STEP_RUNNING,
+    WFS_WAITING: STEP_WAITING,
+    WFS_SUCCEEDED: STEP_SUCCEEDED,
+    WFS_FAILED: STEP_FAILED,
+    WFS_SKIPPED: STEP_SUCCEEDED,
+    WFS_CANCELLED: STEP_CANCELLED,
+}
+
+
+class StepEvent(NamedTuple):
+    """One journaled step transition of a run. `tick` is the device tick that
+    detected it; `between_ticks` marks a pass outside the tick (a cancel)."""
+    run_id: str
+    step: int
+    step_id: str
+    from_state: int
+    to_state: int
+    tick: int
+    between_ticks: bool
+
+
+def timeline_of(kind: int, to_state: int) -> Tuple[str, str, Dict[str, Any]]:
+    """(timeline event type, step status, extra data) of a transition into
+    `to_state` of a step of `kind`: the host engine's event names where it
+    has them, `step_retry_scheduled` and `step_cancelled` where it has none."""
+    status = _STEP_STATUS[to_state]
+    if to_state == WFS_DISPATCHED:
+        return "step_dispatched", status, {}
+    if to_state == WFS_WAITING:
+        return "step_waiting", status, {}
+    if to_state == WFS_SUCCEEDED:
+        if kind == WFK_APPROVAL:
+            return "step_approved", status, {}
+        if kind == WFK_DELAY:
+            return "step_delay_completed", status, {}
+        if kind == WFK_CONDITION:
+            return "step_condition_evaluated", status, {"value": True}
+        return "step_completed", status, {}
+    if to_state == WFS_SKIPPED:
+        return "step_condition_evaluated", status, {"value": False}
+    if to_state == WFS_FAILED:
+        return ("step_rejected" if kind == WFK_APPROVAL else "step_completed"), status, {}
+    if to_state == WFS_CANCELLED:
+        return "step_cancelled", status, {}
+    # back to PENDING: the device's retry, or a for_each window re-entry
+    return "step_retry_scheduled", status, {}
 
 
 def _steps_of(workflow: Any) -> List[Step]:
@@ -95,13 +171,21 @@ def dag_from_workflow(workflow: Any, items_len: int,
 class DeviceRunTable:
     """Run ids over a dynamic-mode `WorkflowPipeline`."""
 
-    def __init__(self, pipe: WorkflowPipeline):
+    def __init__(self, pipe: WorkflowPipeline, store=None, clock=SYSTEM_CLOCK):
         if not getattr(pipe, "dynamic", False):
             raise RuntimeError("DeviceRunTable needs a dynamic-mode pipeline")
         self.pipe = pipe
+        self.store = store                # a WorkflowStore, or None
+        self._clock = clock
+        self._events_on = getattr(pipe, "event_cap", None) is not None
+        self._events: List[StepEvent] = []
+        self._tmpl_of: Dict[str, int] = {}
+        # template id -> (workflow id, step ids or None, step kinds)
+        self._tmpl_info: Dict[int, Tuple[str, Optional[List[str]], List[int]]] = {}
         self._handle: Dict[str, Tuple[int, int]] = {}
         self._run_of: Dict[Tuple[int, int], str] = {}
         self._queue: Deque[Tuple[str, int, int, int]] = deque()
+        self._queued_ids: set = set()     # run ids in _queue
         self._reported: List[Tuple[str, str]] = []  # queued runs cancelled
 
     def __len__(self) -> int:
@@ -114,7 +198,7 @@ class DeviceRunTable:
         return self._handle.get(run_id)
 
     def _known(self, run_id: str) -> bool:
-        return run_id in self._handle or any(q[0] == run_id for q in self._queue)
+        return run_id in self._handle or run_id in self._queued_ids
 
     def _admit(self, reqs) -> int:
         """Admit the requests in order; returns how many got a slot (the
@@ -128,8 +212,33 @@ class DeviceRunTable:
                 break
             self._handle[r[0]] = (slot, gen)
             self._run_of[(slot, gen)] = r[0]
+            self._tmpl_of[r[0]] = r[1]
             n += 1
         return n
+
+    def register(self, workflow: Any, items_len: int = 0,
+                 tick_seconds: float = 1.0) -> Optional[int]:
+        """Lower `workflow` and add it as a template; returns the template id
+        to submit() runs of it with, or None if the workflow must stay on the
+        host engine. Events of such runs carry the workflow's step ids."""
+        dag = dag_from_workflow(workflow, items_len, tick_seconds)
+        if dag is None:
+            return None
+        t = self.pipe.add_template(dag)
+        wf_id = getattr(workflow, "id", None)
+        if wf_id is None and isinstance(workflow, dict):
+            wf_id = workflow.get("id", "")
+        self._tmpl_info[t] = (str(wf_id or ""), [st.id for st in _steps_of(workflow)],
+                              [sp.kind for sp in dag.steps])
+        return t
+
+    def _info(self, template_id: int):
+        info = self._tmpl_info.get(template_id)
+        if info is None:    # added to the pipe directly: kinds from the device
+            row = self.pipe.tmpl_kind[template_id * 64:template_id * 64 + 64]
+            n = int(self.pipe.tmpl_nsteps[template_id])
+            info = self._tmpl_info[template_id] = ("", None, row.cpu().tolist()[:n])
+        return info
 
     def submit(self, run_id: str, template_id: int, cond_bits: int = 0,
                fanout: int = 0) -> bool:
@@ -146,6 +255,7 @@ class DeviceRunTable:
         if not self._queue and self._admit([req]) == 1:
             return True
         self._queue.append(req)
+        self._queued_ids.add(run_id)
         return False
 
     def cancel(self, run_id: str) -> bool:
@@ -155,29 +265,112 @@ class DeviceRunTable:
         for q in self._queue:
             if q[0] == run_id:
                 self._queue.remove(q)
+                self._queued_ids.discard(run_id)
                 self._reported.append((run_id, RUN_CANCELLED))
+                if self.store is not None:
+                    self._store_completion(run_id, RUN_CANCELLED, self._info(q[1])[0])
                 return True
         h = self._handle.get(run_id)
         if h is None:
             return False
         return bool(self.pipe.cancel([h[0]], [h[1]])[0])
 
+    def _drain_events(self) -> None:
+        """Journal records -> StepEvents (and the store). Records of a (slot,
+        gen) this table does not know are dropped."""
+        slots, gens, steps, frm, to, stamps = self.pipe.drain_events()
+        for slot, gen, step, f, t, stamp in zip(slots, gens, steps, frm, to, stamps):
+            run_id = self._run_of.get((slot, gen))
+            if run_id is None:
+                continue
+            wf_id, ids, kinds = self._info(self._tmpl_of[run_id])
+            step_id = ids[step] if ids is not None and step < len(ids) else ""
+            ev = StepEvent(run_id, step, step_id, f, t, stamp >> 1, bool(stamp & 1))
+            self._events.append(ev)
+            if self.store is not None:
+                kind = kinds[step] if step < len(kinds) else WFK_WORKER
+                self._store_event(ev, wf_id, kind)
+
+    def _stored_run(self, run_id: str):
+        try:
+            return self.store.get_run(run_id)
+        except KeyError:                  # RunNotFound: not the store's run
+            return None
+
+    def _store_event(self, ev: StepEvent, wf_id: str, kind: int) -> None:
+        run = self._stored_run(ev.run_id)
+        if run is None:
+            return
+        etype, status, extra = timeline_of(kind, ev.to_state)
+        data = {"tick": ev.tick}
+        data.update(extra)
+        self.store.append_timeline(ev.run_id, TimelineEvent(
+            time=self._clock.now(), type=etype, run_id=ev.run_id,
+            workflow_id=wf_id or run.workflow_id, step_id=ev.step_id,
+            status=status, data=data))
+        if ev.step_id:
+            sr = run.steps.get(ev.step_id)
+            if sr is None:
+                sr = run.steps[ev.step_id] = StepRun(step_id=ev.step_id)
+            sr.status = status
+            self.store.update_run(run)
+
+    def _store_completion(self, run_id: str, status: str, wf_id: str) -> None:
+        run = self._stored_run(run_id)
+        if run is None:
+            return
+        run.status = status
+        run.completed_at = self._clock.now()
+        self.store.update_run(run)
+        self.store.append_timeline(run_id, TimelineEvent(
+            time=self._clock.now(), type="run_status", run_id=run_id,
+            workflow_id=wf_id or run.workflow_id, status=status))
+
+    def take_events(self) -> List[StepEvent]:
+        """The step events the polls gathered since the last call, in time
+        order per run."""
+        out, self._events = self._events, []
+        return out
+
+    def step_states(self, run_id: str) -> Dict[Union[str, int], str]:
+        """Current `STEP_*` status per step of an admitted or queued run, by
+        step id (by step index for a template added without register())."""
+        h = self._handle.get(run_id)
+        if h is None:
+            for q in self._queue:
+                if q[0] == run_id:
+                    _, ids, kinds = self._info(q[1])
+                    return {(ids[s] if ids else s): STEP_PENDING
+                            for s in range(len(kinds))}
+            raise KeyError(run_id)
+        _, ids, kinds = self._info(self._tmpl_of[run_id])
+        row = self.pipe.step_state[h[0] * 64:h[0] * 64 + len(kinds)].cpu().tolist()
+        return {(ids[s] if ids else s): _STEP_STATUS[v] for s, v in enumerate(row)}
+
     def poll(self) -> List[Tuple[str, str]]:
-        """Drain the device's completion records, then admit what is queued.
-        Returns (run_id, status) for every run that ended since the last
-        poll, each exactly once."""
+        """Drain the device's step events (journal on), then its completion
+        records, then admit what is queued. Returns (run_id, status) for
+        every run that ended since the last poll, each exactly once; a run's
+        events are all gathered before its completion is returned."""
         out, self._reported = self._reported, []
+        if self._events_on:
+            # before drain_completed(): a run's last events still find its
+            # handle, and its slot cannot be released with changes unseen
+            self._drain_events()
         slots, gens, states = self.pipe.drain_completed()
         for slot, gen, state in zip(slots, gens, states):
             run_id = self._run_of.pop((slot, gen), None)
             if run_id is None:
                 continue
             del self._handle[run_id]
+            tmpl = self._tmpl_of.pop(run_id)
             out.append((run_id, _STATUS[state]))
+            if self.store is not None:
+                self._store_completion(run_id, _STATUS[state], self._info(tmpl)[0])
         if self._queue:
             reqs = list(self._queue)
             for _ in range(self._admit(reqs)):
-                self._queue.popleft()
+                self._queued_ids.discard(self._queue.popleft()[0])
         return out
 
     def tick(self) -> None:

@@ -16,7 +16,16 @@ in a device synchronise). `admit` and `drain_completed` are timed per call
 with device events (the drain's time includes its D2H copy). Prints one JSON
 line with the median and the min..max spread over the repeats.
 
+With --events [CAP] a third mode joins the alternation: the same churn on a
+pipeline with the step-transition journal on (event_cap CAP, default
+2 * runs * 64, which cannot overflow), driven through `DeviceRunTable`, whose
+poll() drains the journal every tick. It reports runs/s, events/s, the
+`event_overflows` count and the bytes one journal pass has to move at this
+table size (life bytes, plus generations, states and shadow of the rows that
+are not FREE, plus the records written).
+
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5
+    python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --events
 """
 import argparse
 import json
@@ -42,6 +51,9 @@ def main() -> int:
     ap.add_argument("--ticks", type=int, default=200, help="ticks per window")
     ap.add_argument("--warmup", type=int, default=40, help="ticks before the first window")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--events", type=int, nargs="?", const=0, default=None, metavar="CAP",
+                    help="also run the churn with the step journal on "
+                         "(CAP records; default 2 * runs * 64)")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="rehearse the host logic on the reference backend (no timings)")
     args = ap.parse_args()
@@ -112,6 +124,42 @@ def main() -> int:
         sync()
         return ok, time.perf_counter() - t0
 
+    # ---- dynamic mode with the step journal, through DeviceRunTable --------
+    ev_window = None
+    if args.events is not None:
+        from cordum_amd.workflow.device_runs import DeviceRunTable
+
+        ev_cap = args.events or 2 * args.runs * 64
+        evp = WorkflowPipeline(dags=[dag], dynamic_capacity=args.runs,
+                               event_cap=ev_cap, **common)
+        table = DeviceRunTable(evp)
+        next_id = [0]
+        n_events = [0]
+
+        def submit(n):
+            for _ in range(n):
+                table.submit(f"run-{next_id[0]}", 0)
+                next_id[0] += 1
+
+        # twice what the table holds: with submissions always waiting, every
+        # later one queues too and poll() admits them in one batch per tick,
+        # as the plain dynamic window does. The table itself stays full.
+        submit(2 * args.runs)
+        assert table.queued() == args.runs
+
+        def ev_window(n_ticks):
+            ok = 0
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(n_ticks):
+                table.tick()
+                done = table.poll()
+                ok += sum(1 for _, st in done if st == "succeeded")
+                n_events[0] += len(table.take_events())
+                submit(len(done))
+            sync()
+            return ok, time.perf_counter() - t0
+
     # ---- baseline: readmit continuous mode ---------------------------------
     sta = WorkflowPipeline(dags=[dag], replicate=args.runs, **common)
     sta.reset_runs()
@@ -127,18 +175,26 @@ def main() -> int:
         ok1 = sta.counts()[0]          # D2H: ends the window in a synchronise
         return ok1 - ok0, time.perf_counter() - t0
 
-    dyn_window(args.warmup)
-    sta_window(args.warmup)
+    modes = [("dynamic", dyn_window), ("readmit", sta_window)]
+    if ev_window is not None:
+        modes.insert(1, ("events", ev_window))
+    for _, window in modes:
+        window(args.warmup)
     t_admit.take_ms(), t_drain.take_ms(), t_readmit.take_ms()
 
-    rate = {"dynamic": [], "readmit": []}
-    tick_ms = {"dynamic": [], "readmit": []}
+    rate = {name: [] for name, _ in modes}
+    tick_ms = {name: [] for name, _ in modes}
+    ev_rate = []
     call_ms = {"admit": [], "drain_completed": [], "readmit_succeeded": []}
     for _ in range(args.repeats):
-        for name, window in (("dynamic", dyn_window), ("readmit", sta_window)):
+        for name, window in modes:
+            if name == "events":
+                n_events[0] = 0
             ok, dt = window(args.ticks)
             rate[name].append(ok / dt)
             tick_ms[name].append(dt / args.ticks * 1000.0)
+            if name == "events":
+                ev_rate.append(n_events[0] / dt)
         # per-call medians of this repeat
         for key, timer in (("admit", t_admit), ("drain_completed", t_drain),
                            ("readmit_succeeded", t_readmit)):
@@ -162,6 +218,23 @@ def main() -> int:
         "graph": {"dynamic": bool(dyn._wf_graph), "readmit": bool(sta._wf_graph)},
         "live_at_end": live[0],
     }
+    if ev_window is not None:
+        per_tick = statistics.median(ev_rate) * statistics.median(tick_ms["events"]) / 1000.0
+        # one pass: a life byte per slot; generation + shadow generation,
+        # 64 state and 64 shadow bytes per row that is not FREE (the table is
+        # held full); 16 bytes per record written
+        pass_bytes = args.runs * (1 + 4 + 4 + 64 + 64) + 16 * per_tick
+        out["events"] = {
+            "event_cap": ev_cap,
+            "runs_per_s": spread(rate["events"]),
+            "events_per_s": spread(ev_rate),
+            "events_over_dynamic": round(
+                statistics.median(rate["events"]) / max(1e-9, statistics.median(rate["dynamic"])), 3),
+            "event_overflows": evp.event_overflows,
+            "events_per_tick": round(per_tick, 1),
+            "journal_bytes_per_pass": int(pass_bytes),
+            "graph": bool(evp._wf_graph),
+        }
     print(json.dumps(out))
     return 0
 
