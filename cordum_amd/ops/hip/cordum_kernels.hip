@@ -1445,6 +1445,284 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K3-WF externally decided approvals: hold scan / hold list / decide
+// ---------------------------------------------------------------------------
+// With approvals decided from outside, an APPROVAL step that wf_sweep set
+// WAITING stays WAITING until wf_decide names it by (slot, gen, step). The
+// hold tables remember since when: hold_mask[r] bit s = step s has an open
+// hold, hold_tick[r*64+s] = the tick it opened, hold_ttl[r*64+s] = ticks
+// until it expires (0 = never). A row's hold data counts only while
+//   hold_gen[r] == run_gen[r] && run_life[r] == LIVE && run_active[r] == 1;
+// otherwise it is empty, whatever the words hold: a slot can be cancelled,
+// drained and re-admitted between two ticks with no pass in between.
+//
+// wf_hold_scan runs inside the tick, directly after wf_sweep. Layout as the
+// journal: 4 lanes per row, 16 steps (one 16-byte state load) per lane, 16
+// rows per wave, 64 rows per block; the four lanes of a row OR their 16 mask
+// bits together with two xor-shuffles and lane q == 0 owns the mask word. A
+// wave with no WAITING byte, no open hold and no generation change does
+// nothing more after the loads and writes nothing; it never touches
+// hold_tick / hold_ttl, which are read only for a hold that continues. The
+// tables after a pass are a pure function of the tables before it; the
+// atomics are the cumulative counters (opened, expired) and the open-hold
+// gauge, at most one add per block each.
+//
+// A hold opened at tick h with ttl T expires in the pass of tick h + T if it
+// is still WAITING then: the step becomes FAILED, wf_status fails the run
+// later in the same tick.
+__global__ __launch_bounds__(BLOCK) void wf_hold_scan_kernel(
+    unsigned char* __restrict__ step_state,         // [NR*64]
+    const unsigned char* __restrict__ n_steps,      // [NR]
+    const unsigned char* __restrict__ run_life,     // [NR]
+    const unsigned char* __restrict__ run_active,   // [NR]
+    const int* __restrict__ run_gen,                // [NR]
+    const int* __restrict__ tick_p,
+    const int* __restrict__ hold_ttl,               // [NR*64]
+    unsigned long long* __restrict__ hold_mask,     // [NR]
+    int* __restrict__ hold_tick,                    // [NR*64]
+    int* __restrict__ hold_gen,                     // [NR]
+    unsigned long long* __restrict__ hold_counts,   // [4] opened, expired, ...
+    int* __restrict__ hold_open,                    // [1]
+    int NR)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int r = t >> 2;                           // 4 lanes per row
+    const int q = t & 3;                            // steps 16q .. 16q+15
+    const int life = r < NR ? (int)run_life[r] : WFL_FREE;
+    const size_t off = (size_t)r * 64 + (size_t)q * 16;
+    bool act = false, match = false;
+    int gen = 0;
+    unsigned long long raw = 0ull;                  // the mask word as stored
+    unsigned wait = 0u;                             // bit j: step 16q+j is WAITING
+    if (life != WFL_FREE) {
+        gen = run_gen[r];
+        match = hold_gen[r] == gen;
+        raw = hold_mask[r];
+        act = life == WFL_LIVE && run_active[r] == 1;
+        // the states of a LIVE row are loaded with the narrow words above,
+        // not after the active byte: one dependent round less for the rows
+        // that matter, 64 bytes read in vain for a terminal, unreported one
+        uint4 st = make_uint4(0u, 0u, 0u, 0u);
+        if (life == WFL_LIVE) st = *reinterpret_cast<const uint4*>(step_state + off);
+        if (act) {
+            const unsigned sw[4] = {st.x, st.y, st.z, st.w};
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                wait |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_WAITING) << j;
+            if (wait != 0u) {                       // bytes at s >= n_steps are no steps
+                const int left = (int)n_steps[r] - q * 16;
+                wait &= left >= 16 ? 0xffffu : left <= 0 ? 0u : (1u << left) - 1u;
+            }
+        }
+    }
+    const unsigned long long old = match ? raw : 0ull;   // the mask that counts
+    // work: a WAITING step, an open hold to look at or to clear, or a row
+    // admitted since its hold words were written. A wave without any skips
+    // to the block's counter sum below.
+    const bool busy = __any(wait != 0u || (match && raw != 0ull) || (act && !match));
+
+    const int tick = *tick_p;
+    const unsigned oldq = (unsigned)(old >> (q * 16)) & 0xffffu;
+    unsigned keep = 0u;                             // this lane's 16 bits after the pass
+    int opened = 0, expired = 0;
+    if (busy && act) {
+        const unsigned fresh = wait & ~oldq;
+        unsigned cont = wait & oldq;
+        keep = wait;
+        opened = __popc(fresh);
+#pragma unroll 1
+        for (unsigned f = fresh; f != 0u; f &= f - 1u)
+            hold_tick[off + (__ffs((int)f) - 1)] = tick;
+#pragma unroll 1
+        for (; cont != 0u; cont &= cont - 1u) {
+            const int j = __ffs((int)cont) - 1;
+            const int ttl = hold_ttl[off + j];
+            if (ttl > 0 && tick - hold_tick[off + j] >= ttl) {
+                step_state[off + j] = WFS_FAILED;
+                keep &= ~(1u << j);
+                ++expired;
+            }
+        }
+    }
+    unsigned long long acc = 0ull;
+    if (busy) {                                     // wave-uniform
+        // the row's new mask: OR of its four lanes' bits (lanes 4k .. 4k+3)
+        unsigned long long now = (unsigned long long)keep << (q * 16);
+        now |= __shfl_xor(now, 1, WAVE);
+        now |= __shfl_xor(now, 2, WAVE);
+        int open = 0;
+        if (q == 0 && life != WFL_FREE) {
+            if (act) {
+                if (now != raw) hold_mask[r] = now;
+                if (!match) hold_gen[r] = gen;
+                open = __popcll(now);
+            } else if (match && raw != 0ull) {
+                hold_mask[r] = 0ull;                // cancelled or finished with holds open
+            }
+        }
+        // wave totals in one butterfly: three 21-bit fields (each <= 1024)
+        acc = (unsigned long long)opened | (unsigned long long)expired << 21
+            | (unsigned long long)open << 42;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) acc += __shfl_xor(acc, d, WAVE);
+    }
+    // one add per counter and block, not per wave: with a hold open in most
+    // rows of a large table every wave has something to add, and adds to one
+    // word are served one after the other
+    __shared__ unsigned long long part[BLOCK / WAVE];
+    if (threadIdx.x % WAVE == 0) part[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
+        const unsigned long long no = sum & 0x1fffffull, ne = (sum >> 21) & 0x1fffffull;
+        const int nopen = (int)(sum >> 42);         // each field <= 4096
+        if (no) atomicAdd(&hold_counts[0], no);
+        if (ne) atomicAdd(&hold_counts[1], ne);
+        if (nopen) atomicAdd(hold_open, nopen);
+    }
+}
+
+// hold listing, pass 1 of 3 (between ticks): one thread per row. A row's
+// listable holds are its valid mask bits whose step is still WAITING and
+// whose key slot*64+step is at or after the cursor; only a row with a
+// nonzero valid mask reads its states. The filtered mask is kept for the
+// write pass (a snapshot, so both passes agree), its popcounts are summed
+// per 256-row block for the scan (wf_admit_scan_kernel).
+__global__ __launch_bounds__(BLOCK) void wf_hold_list_count_kernel(
+    const unsigned char* __restrict__ step_state,   // [NR*64]
+    const unsigned char* __restrict__ run_life,
+    const unsigned char* __restrict__ run_active,
+    const int* __restrict__ run_gen,
+    const unsigned long long* __restrict__ hold_mask,
+    const int* __restrict__ hold_gen,
+    long long cursor,
+    unsigned long long* __restrict__ list_mask,     // [NR] workspace
+    int* __restrict__ blk_scan,                     // [nblk+1] counts, scanned next
+    int NR)
+{
+    __shared__ int cnt[BLOCK / WAVE];
+    const int r = blockIdx.x * BLOCK + threadIdx.x;
+    unsigned long long m = 0ull;
+    if (r < NR) {
+        if (run_life[r] == WFL_LIVE && run_active[r] == 1 && hold_gen[r] == run_gen[r])
+            m = hold_mask[r];
+        const long long key0 = (long long)r * 64;
+        if (key0 + 63 < cursor) m = 0ull;
+        else if (key0 < cursor) m &= ~0ull << (int)(cursor - key0);   // shift 1..63
+        if (m != 0ull) {
+            const uint4* row = reinterpret_cast<const uint4*>(step_state + (size_t)r * 64);
+            unsigned long long w = 0ull;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint4 st = row[k];
+                const unsigned sw[4] = {st.x, st.y, st.z, st.w};
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    w |= (unsigned long long)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu)
+                                              == WFS_WAITING) << (k * 16 + j);
+            }
+            m &= w;
+        }
+        list_mask[r] = m;
+    }
+    int n = __popcll(m);
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) n += __shfl_xor(n, d, WAVE);
+    if (threadIdx.x % WAVE == 0) cnt[threadIdx.x / WAVE] = n;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        blk_scan[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+// hold listing, pass 3: the ordered write. Row r's records start at the
+// scanned count of its block plus the popcounts of the rows before it in
+// the block, so positions ascend with (slot, step) and a full page holds
+// exactly the cap lowest keys. list[0] = the number that matched.
+__global__ __launch_bounds__(BLOCK) void wf_hold_list_write_kernel(
+    const unsigned long long* __restrict__ list_mask,   // [NR]
+    const int* __restrict__ blk_scan,               // [nblk+1] scanned
+    const int* __restrict__ run_gen,
+    const int* __restrict__ hold_tick,              // [NR*64]
+    int* __restrict__ list,                         // [4 + cap*4]
+    int NR, int nblk, int cap)
+{
+    __shared__ int wsum[BLOCK / WAVE];
+    const int r = blockIdx.x * BLOCK + threadIdx.x;
+    const int lane = threadIdx.x % WAVE;
+    const int w = threadIdx.x / WAVE;
+    unsigned long long m = r < NR ? list_mask[r] : 0ull;
+    const int n = __popcll(m);
+    int incl = n;                                   // inclusive wave prefix sum
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int v = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += v;
+    }
+    if (lane == WAVE - 1) wsum[w] = incl;
+    __syncthreads();
+    int pos = blk_scan[blockIdx.x] + incl - n;
+    for (int k = 0; k < w; ++k) pos += wsum[k];
+    if (r == 0) list[0] = blk_scan[nblk];
+    if (m == 0ull || pos >= cap) return;
+    const int gen = run_gen[r];
+    for (; m != 0ull && pos < cap; m &= m - 1ull, ++pos) {
+        const int s = __ffsll((long long)m) - 1;
+        *reinterpret_cast<int4*>(list + 4 + (size_t)pos * 4) =
+            make_int4(r, gen, s, hold_tick[(size_t)r * 64 + s]);
+    }
+}
+
+// decisions (between ticks): one thread per request, distinct (slot, step)
+// pairs (the host sends only the first of a repeated pair). Result codes:
+// 0 applied, 1 stale handle, 2 run no longer active, 3 not a waiting
+// approval. It writes the one state byte; the next scan closes the hold and
+// wf_hold_list already filters on the state.
+__global__ __launch_bounds__(BLOCK) void wf_decide_kernel(
+    const int* __restrict__ req_slot,               // [n]
+    const int* __restrict__ req_gen,
+    const int* __restrict__ req_step,
+    const int* __restrict__ req_verdict,
+    int n,
+    const unsigned char* __restrict__ run_life,
+    const int* __restrict__ run_gen,
+    const unsigned char* __restrict__ run_active,
+    const unsigned char* __restrict__ n_steps,
+    const unsigned char* __restrict__ step_kind,    // [NR*64]
+    unsigned char* __restrict__ step_state,         // [NR*64]
+    unsigned long long* __restrict__ hold_counts,   // [4] ..., approved, rejected
+    unsigned char* __restrict__ out_code,           // [n]
+    int NR)
+{
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    bool yes = false, no = false;
+    if (i < n) {
+        const int slot = req_slot[i], step = req_step[i];
+        int code = 0;
+        if (slot < 0 || slot >= NR || run_life[slot] != WFL_LIVE
+            || run_gen[slot] != req_gen[i])
+            code = 1;
+        else if (run_active[slot] != 1)
+            code = 2;
+        else if (step < 0 || step >= (int)n_steps[slot]
+                 || step_kind[(size_t)slot * 64 + step] != WFK_APPROVAL
+                 || step_state[(size_t)slot * 64 + step] != WFS_WAITING)
+            code = 3;
+        if (code == 0) {
+            yes = req_verdict[i] != 0;
+            no = !yes;
+            step_state[(size_t)slot * 64 + step] = yes ? WFS_SUCCEEDED : WFS_FAILED;
+        }
+        out_code[i] = (unsigned char)code;
+    }
+    // one add per counter and wave
+    const unsigned long long ym = __ballot(yes), nm = __ballot(no);
+    if (threadIdx.x % WAVE == 0) {
+        if (ym) atomicAdd(&hold_counts[2], (unsigned long long)__popcll(ym));
+        if (nm) atomicAdd(&hold_counts[3], (unsigned long long)__popcll(nm));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K4: deadline / staleness scan -> TIMEOUT candidates (compacted list)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void deadline_scan_kernel(
@@ -3189,6 +3467,105 @@ void wf_journal(torch::Tensor step_state, torch::Tensor run_life, torch::Tensor 
         ev_rec.data_ptr<int>(), ev_count.data_ptr<int>(), (int)NR, (int)cap);
 }
 
+// one hold scan on the current stream (inside the tick, after wf_sweep); the
+// caller zeroes hold_open first
+void wf_hold_scan(torch::Tensor step_state, torch::Tensor n_steps, torch::Tensor run_life,
+                  torch::Tensor run_active, torch::Tensor run_gen, torch::Tensor tick,
+                  torch::Tensor hold_ttl, torch::Tensor hold_mask, torch::Tensor hold_tick,
+                  torch::Tensor hold_gen, torch::Tensor hold_counts, torch::Tensor hold_open)
+{
+    const int64_t NR = run_life.numel();
+    if (NR <= 0) return;
+    TORCH_CHECK(step_state.numel() == NR * 64 && hold_ttl.numel() == NR * 64
+                && hold_tick.numel() == NR * 64 && n_steps.numel() == NR
+                && run_active.numel() == NR && run_gen.numel() == NR
+                && hold_mask.numel() == NR && hold_gen.numel() == NR,
+                "wf_hold_scan: table sizes disagree");
+    TORCH_CHECK(hold_counts.numel() >= 4 && hold_open.numel() >= 1 && tick.numel() >= 1,
+                "wf_hold_scan: counters need 4 + 1 words");
+    TORCH_CHECK(step_state.is_contiguous() && hold_ttl.is_contiguous()
+                && hold_tick.is_contiguous() && hold_mask.is_contiguous(),
+                "wf_hold_scan: tables must be contiguous");
+    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_hold_scan: table too large");
+    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0,
+                "wf_hold_scan: states must be 16-byte aligned");
+    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(wf_hold_scan_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        step_state.data_ptr<uint8_t>(), n_steps.data_ptr<uint8_t>(),
+        run_life.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
+        run_gen.data_ptr<int>(), tick.data_ptr<int>(), hold_ttl.data_ptr<int>(),
+        (unsigned long long*)hold_mask.data_ptr<int64_t>(), hold_tick.data_ptr<int>(),
+        hold_gen.data_ptr<int>(), (unsigned long long*)hold_counts.data_ptr<int64_t>(),
+        hold_open.data_ptr<int>(), (int)NR);
+}
+
+// one page of open holds, three launches on the current stream. list is
+// [count, pad x3 | cap records of 4 words]; list_mask / blk_scan are
+// caller-owned workspaces ([NR] int64, [nblk+1] int32, nblk = ceil(NR/256))
+void wf_hold_list(torch::Tensor step_state, torch::Tensor run_life, torch::Tensor run_active,
+                  torch::Tensor run_gen, torch::Tensor hold_mask, torch::Tensor hold_tick,
+                  torch::Tensor hold_gen, int64_t cursor,
+                  torch::Tensor list_mask, torch::Tensor blk_scan, torch::Tensor list)
+{
+    const int64_t NR = run_life.numel();
+    if (NR <= 0) return;
+    const int nblk = (int)((NR + BLOCK - 1) / BLOCK);
+    const int64_t cap = (list.numel() - 4) / 4;
+    TORCH_CHECK(step_state.numel() == NR * 64 && hold_tick.numel() == NR * 64
+                && run_active.numel() == NR && run_gen.numel() == NR
+                && hold_mask.numel() == NR && hold_gen.numel() == NR,
+                "wf_hold_list: table sizes disagree");
+    TORCH_CHECK(list_mask.numel() >= NR && blk_scan.numel() >= nblk + 1,
+                "wf_hold_list: workspace too small");
+    TORCH_CHECK(cap >= 1 && list.numel() == 4 + cap * 4 && cap <= (int64_t)INT_MAX,
+                "wf_hold_list: the list needs 4 + cap*4 words, cap >= 1");
+    TORCH_CHECK(step_state.is_contiguous() && list.is_contiguous()
+                && hold_tick.is_contiguous(), "wf_hold_list: tables must be contiguous");
+    TORCH_CHECK(NR * 64 <= (int64_t)INT_MAX, "wf_hold_list: table too large");
+    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
+                && (uintptr_t)list.data_ptr<int>() % 16 == 0,
+                "wf_hold_list: states and list must be 16-byte aligned");
+    hipLaunchKernelGGL(wf_hold_list_count_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
+        step_state.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
+        run_active.data_ptr<uint8_t>(), run_gen.data_ptr<int>(),
+        (const unsigned long long*)hold_mask.data_ptr<int64_t>(), hold_gen.data_ptr<int>(),
+        (long long)cursor, (unsigned long long*)list_mask.data_ptr<int64_t>(),
+        blk_scan.data_ptr<int>(), (int)NR);
+    hipLaunchKernelGGL(wf_admit_scan_kernel, dim3(1), dim3(BLOCK), 0, cur_stream(),
+        blk_scan.data_ptr<int>(), nblk);
+    hipLaunchKernelGGL(wf_hold_list_write_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
+        (const unsigned long long*)list_mask.data_ptr<int64_t>(), blk_scan.data_ptr<int>(),
+        run_gen.data_ptr<int>(), hold_tick.data_ptr<int>(), list.data_ptr<int>(),
+        (int)NR, nblk, (int)cap);
+}
+
+void wf_decide(torch::Tensor req_slot, torch::Tensor req_gen, torch::Tensor req_step,
+               torch::Tensor req_verdict,
+               torch::Tensor run_life, torch::Tensor run_gen, torch::Tensor run_active,
+               torch::Tensor n_steps, torch::Tensor step_kind, torch::Tensor step_state,
+               torch::Tensor hold_counts, torch::Tensor out_code)
+{
+    const int n = (int)req_slot.size(0);
+    if (n <= 0) return;
+    const int64_t NR = n_steps.size(0);
+    TORCH_CHECK(req_gen.size(0) >= n && req_step.size(0) >= n && req_verdict.size(0) >= n
+                && out_code.size(0) >= n,
+                "wf_decide: request/output arrays shorter than the request count");
+    TORCH_CHECK(step_state.numel() == NR * 64 && step_kind.numel() == NR * 64
+                && run_life.numel() == NR && run_gen.numel() == NR
+                && run_active.numel() == NR && hold_counts.numel() >= 4,
+                "wf_decide: table sizes disagree");
+    const int blocks = (n + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(wf_decide_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        req_slot.data_ptr<int>(), req_gen.data_ptr<int>(), req_step.data_ptr<int>(),
+        req_verdict.data_ptr<int>(), n,
+        run_life.data_ptr<uint8_t>(), run_gen.data_ptr<int>(),
+        run_active.data_ptr<uint8_t>(), n_steps.data_ptr<uint8_t>(),
+        step_kind.data_ptr<uint8_t>(), step_state.data_ptr<uint8_t>(),
+        (unsigned long long*)hold_counts.data_ptr<int64_t>(),
+        out_code.data_ptr<uint8_t>(), (int)NR);
+}
+
 void materialize_rq_payload(torch::Tensor payload, torch::Tensor rq_prev_payload,
                             torch::Tensor rq_src, torch::Tensor rq_count,
                             torch::Tensor rq_payload, int64_t stride)
@@ -3476,6 +3853,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_cancel", &wf_cancel, "K3-WF generation-checked run cancellation");
     m.def("wf_retire", &wf_retire, "K3-WF completion records + quiescent slot release");
     m.def("wf_journal", &wf_journal, "K3-WF step-transition journal pass (observer)");
+    m.def("wf_hold_scan", &wf_hold_scan, "K3-WF approval hold scan (open / expire / close holds)");
+    m.def("wf_hold_list", &wf_hold_list, "K3-WF ordered page of open approval holds");
+    m.def("wf_decide", &wf_decide, "K3-WF generation-checked approval decisions");
     m.def("materialize_rq_payload", &materialize_rq_payload, "copy requeued payload rows into the rq arena");
     m.def("gather_payload_padded", &gather_payload_padded, "payload gather into padded send arena");
     m.def("echo_padded", &echo_padded, "region-valid echo over padded recv arena");

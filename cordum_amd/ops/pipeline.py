@@ -349,6 +349,21 @@ class _RefOps:
 
         wf_journal_ref(st, rl, rg, tick, int(phase), shs, shg, rec, cnt)
 
+    def wf_hold_scan(self, *a):
+        from .reference import wf_hold_scan_ref
+
+        wf_hold_scan_ref(*a)
+
+    def wf_hold_list(self, st, rl, ra, rg, hm, ht, hg, cursor, lm, bs, out):
+        from .reference import wf_hold_list_ref
+
+        wf_hold_list_ref(st, rl, ra, rg, hm, ht, hg, int(cursor), lm, bs, out)
+
+    def wf_decide(self, *a):
+        from .reference import wf_decide_ref
+
+        wf_decide_ref(*a)
+
     def materialize_rq_payload(self, payload, prev_payload, rq_src, rq_count,
                                rq_payload, stride):
         from .reference import materialize_rq_payload_ref

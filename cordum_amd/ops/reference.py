@@ -702,3 +702,113 @@ def wf_journal_ref(step_state, run_life, run_gen, tick, phase: int,
     rec[:, 3] = stamp
     sh[rows, steps] = st[rows, steps]
     ev_count[0] = count + k
+
+
+# -- K3-WF externally decided approvals (hold scan / hold list / decide) --------
+# A row's hold data counts only while hold_gen == run_gen, the row is LIVE and
+# run_active == 1; otherwise it is empty, whatever the words hold.
+
+_M64 = (1 << 64) - 1
+
+
+def _to_i64(m: int) -> int:
+    return m - (1 << 64) if m >= (1 << 63) else m
+
+
+def wf_hold_scan_ref(step_state, n_steps, run_life, run_active, run_gen, tick,
+                     hold_ttl, hold_mask, hold_tick, hold_gen, hold_counts,
+                     hold_open):
+    """One hold scan (inside the tick, after the sweep). Per LIVE and active
+    row: a WAITING step with its bit clear opens a hold stamped `tick`; a
+    continuing hold whose ttl has run out (tick - hold_tick >= ttl > 0) fails
+    its step; a bit whose step left WAITING is cleared. A generation change
+    empties the mask first. Rows that are not LIVE-and-active lose a valid
+    nonzero mask; FREE rows are not visited. hold_open gains the number of
+    bits left set."""
+    NR = int(run_life.shape[0])
+    now = int(tick[0])
+    life = run_life[:NR]
+    act = (life == WFL_LIVE) & (run_active[:NR] == 1)
+    match = hold_gen[:NR] == run_gen[:NR]
+    hold_mask[(life != WFL_FREE) & ~act & match & (hold_mask[:NR] != 0)] = 0
+    st = step_state.view(NR, 64)
+    waiting = (st == WFS_WAITING) & (torch.arange(64)[None, :] < n_steps[:NR, None])
+    rows = torch.nonzero(act & (waiting.any(dim=1) | ~match | (hold_mask[:NR] != 0)))
+    opened = expired = still = 0
+    for r in rows.flatten().tolist():
+        raw = int(hold_mask[r]) & _M64
+        old = raw if bool(match[r]) else 0
+        new = 0
+        for s in torch.nonzero(waiting[r]).flatten().tolist():
+            i = r * 64 + s
+            if not (old >> s) & 1:
+                hold_tick[i] = now
+                opened += 1
+            else:
+                ttl = int(hold_ttl[i])
+                if ttl > 0 and now - int(hold_tick[i]) >= ttl:
+                    step_state[i] = WFS_FAILED
+                    expired += 1
+                    continue
+            new |= 1 << s
+        if new != raw:
+            hold_mask[r] = _to_i64(new)
+        if not bool(match[r]):
+            hold_gen[r] = int(run_gen[r])
+        still += bin(new).count("1")
+    hold_counts[0] += opened
+    hold_counts[1] += expired
+    hold_open[0] += still
+
+
+def wf_hold_list_ref(step_state, run_life, run_active, run_gen, hold_mask,
+                     hold_tick, hold_gen, cursor: int, list_mask, blk_scan, out):
+    """One page of open holds in ascending (slot, step): out[0] is the number
+    of holds with key slot*64+step >= cursor, out[4:] the records (slot, gen,
+    step, hold_tick) of the lowest min(count, cap) of them. list_mask /
+    blk_scan are the kernel's workspaces: unused."""
+    NR = int(run_life.shape[0])
+    cap = (int(out.shape[0]) - 4) // 4
+    valid = ((run_life[:NR] == WFL_LIVE) & (run_active[:NR] == 1)
+             & (hold_gen[:NR] == run_gen[:NR]) & (hold_mask[:NR] != 0))
+    rec = out[4:].view(-1, 4)
+    count = 0
+    for r in torch.nonzero(valid).flatten().tolist():
+        m = int(hold_mask[r]) & _M64
+        while m:                                   # set bits, ascending
+            s = (m & -m).bit_length() - 1
+            m &= m - 1
+            if r * 64 + s < cursor or int(step_state[r * 64 + s]) != WFS_WAITING:
+                continue
+            if count < cap:
+                rec[count, 0] = r
+                rec[count, 1] = int(run_gen[r])
+                rec[count, 2] = s
+                rec[count, 3] = int(hold_tick[r * 64 + s])
+            count += 1
+    out[0] = count
+
+
+def wf_decide_ref(req_slot, req_gen, req_step, req_verdict, run_life, run_gen,
+                  run_active, n_steps, step_kind, step_state, hold_counts,
+                  out_code):
+    """Decisions by (slot, gen, step): code 0 applied (verdict 1 -> SUCCEEDED,
+    0 -> FAILED), 1 stale handle, 2 run no longer active, 3 not a waiting
+    approval. The hold tables are not touched."""
+    NR = int(n_steps.shape[0])
+    for i in range(int(req_slot.shape[0])):
+        slot, step = int(req_slot[i]), int(req_step[i])
+        if (not 0 <= slot < NR or int(run_life[slot]) != WFL_LIVE
+                or int(run_gen[slot]) != int(req_gen[i])):
+            out_code[i] = 1
+        elif int(run_active[slot]) != 1:
+            out_code[i] = 2
+        elif (not 0 <= step < int(n_steps[slot])
+              or int(step_kind[slot * 64 + step]) != WFK_APPROVAL
+              or int(step_state[slot * 64 + step]) != WFS_WAITING):
+            out_code[i] = 3
+        else:
+            yes = int(req_verdict[i]) != 0
+            step_state[slot * 64 + step] = WFS_SUCCEEDED if yes else WFS_FAILED
+            hold_counts[2 if yes else 3] += 1
+            out_code[i] = 0

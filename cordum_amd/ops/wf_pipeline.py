@@ -43,6 +43,13 @@ more kernel (wf_journal) ends the tick and appends a record per step whose
 state changed since it last looked, and drain_events() returns them (see
 "step-transition journal" below). Without it nothing is allocated and the
 tick launches exactly the sequence above.
+
+With `approvals="external"` dynamic mode serves approval gates per run: the
+host hop above is gone, a hold stays WAITING until decide() names it by
+(slot, gen, step), open_holds() lists what is waiting and a step's
+`ttl_ticks` lets a hold expire (see "externally decided approvals" below).
+One more kernel (wf_hold_scan) follows the sweep. With the default
+`approvals="auto"` nothing is allocated and the tick is unchanged.
 """
 from __future__ import annotations
 
@@ -71,6 +78,7 @@ class StepSpec:
     delay_ticks: int = 0     # DELAY gate
     cond: bool = True        # CONDITION value (pre-evaluated)
     max_parallel: int = 0    # for_each window (0 = unlimited)
+    ttl_ticks: int = 0       # APPROVAL hold expiry (0 = never; external approvals)
 
 
 @dataclass
@@ -129,7 +137,26 @@ class WorkflowPipeline:
         # dynamic mode only: journal every step transition into a device list
         # of this many records (see "step-transition journal")
         event_cap: Optional[int] = None,
+        # dynamic mode only: "external" leaves every approval hold WAITING
+        # until decide() settles it (see "externally decided approvals");
+        # hold_cap is the page size of open_holds()
+        approvals: str = "auto",
+        hold_cap: Optional[int] = None,
     ):
+        if approvals not in ("auto", "external"):
+            raise ValueError("approvals must be 'auto' or 'external'")
+        self.external = approvals == "external"
+        if self.external and dynamic_capacity is None:
+            raise ValueError("approvals='external' needs dynamic_capacity: a "
+                             "decision names a run by (slot, generation)")
+        if hold_cap is not None:
+            if not self.external:
+                raise ValueError("hold_cap needs approvals='external'")
+            if int(hold_cap) < 1:
+                raise ValueError("hold_cap must be >= 1")
+        self.hold_cap = hold_cap
+        if not self.external and any(s.ttl_ticks for dg in dags for s in dg.steps):
+            raise ValueError("ttl_ticks needs approvals='external'")
         if event_cap is not None:
             if dynamic_capacity is None:
                 raise ValueError("event_cap needs dynamic_capacity: the journal "
@@ -397,6 +424,28 @@ class WorkflowPipeline:
                                        device=d)
             self.ev_count = self._ev_buf[0:1]
             self.ev_rec = self._ev_buf[4:]
+        if self.external:
+            # hold tables (see "externally decided approvals"). hold_gen starts
+            # at generation 0, which no admitted run ever has. The page buffer
+            # is [count, pad x3 | records], records 16-byte aligned.
+            if 64 * NR + 1024 > (1 << 31) - 1:
+                raise ValueError("64 * dynamic_capacity must stay below 2^31 "
+                                 "(hold keys and counts are 32-bit)")
+            if self.hold_cap is None:
+                self.hold_cap = min(64 * NR, 65536)
+            self.hold_cap = int(self.hold_cap)
+            self.tmpl_ttl = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+            self._any_ttl = False
+            self.hold_mask = torch.zeros(NR, dtype=torch.int64, device=d)
+            self.hold_tick = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+            self.hold_ttl = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+            self.hold_gen = torch.zeros(NR, dtype=torch.int32, device=d)
+            self.hold_counts = torch.zeros(4, dtype=torch.int64, device=d)
+            self.hold_open = torch.zeros(1, dtype=torch.int32, device=d)
+            self._hold_buf = torch.zeros(4 + 4 * self.hold_cap, dtype=torch.int32,
+                                         device=d)
+            self._hold_list_mask = torch.zeros(NR, dtype=torch.int64, device=d)
+            self._hold_blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
         for dag in templates:
             self.add_template(dag)
         self._capture_dynamic()
@@ -419,6 +468,12 @@ class WorkflowPipeline:
             if spec.kind == WFK_FOR_EACH and spec.fanout > self.CB:
                 raise ValueError(f"fanout {spec.fanout} can never be emitted "
                                  f"(child arena {self.CB})")
+            if spec.ttl_ticks:
+                if not self.external:
+                    raise ValueError("ttl_ticks needs approvals='external'")
+                if spec.kind != WFK_APPROVAL or spec.ttl_ticks < 0:
+                    raise ValueError("ttl_ticks is a positive tick count on an "
+                                     "APPROVAL step")
         deps = torch.zeros(64, dtype=torch.int64)
         kinds = torch.zeros(64, dtype=torch.uint8)
         todo = torch.zeros(64, dtype=torch.int32)
@@ -447,6 +502,11 @@ class WorkflowPipeline:
         self.tmpl_maxp[row].copy_(maxp)
         self.tmpl_delay[row].copy_(delay)
         self.tmpl_nsteps[t:t + 1].fill_(len(dag.steps))
+        if self.external:
+            ttl = torch.tensor([sp.ttl_ticks for sp in dag.steps]
+                               + [0] * (64 - len(dag.steps)), dtype=torch.int32)
+            self.tmpl_ttl[row].copy_(ttl)
+            self._any_ttl = self._any_ttl or bool(ttl.any())
         self._tmpl_cond.append(cbits - (1 << 64) if cbits >= (1 << 63) else cbits)
         self.n_templates = t + 1
         return t
@@ -492,6 +552,13 @@ class WorkflowPipeline:
             self.run_state, self.run_active, self.run_life, self.run_gen,
             self.tick_buf, self._free_mask, self._blk_scan,
             out[:n], out[n:], self.admit_count)
+        if self.external and self._any_ttl:
+            # hold_ttl is a run column like max_parallel: the template's row
+            # goes into every slot just filled (all zero until a template
+            # carries a ttl, so nothing to copy before that)
+            ok = out[:n] >= 0
+            self.hold_ttl.view(-1, 64)[out[:n][ok].long()] = \
+                self.tmpl_ttl.view(-1, 64)[req[2 * n:3 * n][ok].long()]
         h = out.cpu()
         return h[:n].tolist(), h[n:].tolist()
 
@@ -608,6 +675,93 @@ class WorkflowPipeline:
         self.event_overflows += int(overflowed)
         return tuple(cols)
 
+    # ---- externally decided approvals (dynamic mode, approvals="external") ---
+    # An APPROVAL step the sweep set WAITING is a hold. wf_hold_scan, directly
+    # after the sweep in every tick, keeps the hold tables in step with the
+    # run table: hold_mask[r] bit s = step s has an open hold, hold_tick the
+    # tick it opened, hold_ttl its expiry in ticks (0 = never; the template's
+    # ttl_ticks, copied at admission). A row's hold data counts only while
+    # hold_gen[r] == run_gen[r], the row is LIVE and run_active[r] == 1: a
+    # slot can change hands between two ticks with no pass in between, so a
+    # stale row must read as empty rather than be cleaned up in time.
+    #
+    # Timing contract:
+    # - a hold opened at tick h with ttl_ticks = T expires in the scan of tick
+    #   h + T if it is still WAITING then (the step FAILS, the run fails in
+    #   that tick); a decision made before that tick wins;
+    # - a decision made between tick k and k+1 is seen by the sweep of tick
+    #   k+1: dependents dispatch in that tick, and the journal records
+    #   WAITING -> SUCCEEDED with tick k+1, phase 0;
+    # - decide() writes the one state byte; the next scan closes the hold, and
+    #   open_holds() filters on the state, so a decided hold is gone at once.
+    # The tables are rank-local; world > 1 runs the same scan eagerly.
+    def _require_external(self, what: str) -> None:
+        self._require_dynamic(True, what)
+        if not self.external:
+            raise RuntimeError(f"{what} needs approvals='external'")
+
+    def open_holds(self):
+        """Every open hold as (slots, gens, steps, since_ticks), ascending in
+        (slot, step). The device returns pages of hold_cap records, each an
+        exact prefix of what is left, so paging never skips or repeats."""
+        self._require_external("open_holds")
+        cap = self.hold_cap
+        cols: List[List[int]] = [[], [], [], []]
+        cursor = 0
+        while True:
+            self.ext.wf_hold_list(self.step_state, self.run_life, self.run_active,
+                                  self.run_gen, self.hold_mask, self.hold_tick,
+                                  self.hold_gen, cursor, self._hold_list_mask,
+                                  self._hold_blk_scan, self._hold_buf)
+            n = int(self._hold_buf[0:1].cpu()[0])    # synchronising
+            m = min(n, cap)
+            if m:
+                rec = self._hold_buf[4:4 + 4 * m].cpu().view(m, 4)
+                for c, v in zip(cols, rec.t().tolist()):
+                    c.extend(v)
+            if n <= cap:
+                break
+            cursor = cols[0][-1] * 64 + cols[2][-1] + 1
+        return tuple(cols)
+
+    def decide(self, slots: Sequence[int], gens: Sequence[int],
+               steps: Sequence[int], verdicts: Sequence[int]) -> List[int]:
+        """Approve (verdict 1) or reject (0) the holds named by (slot, gen,
+        step); returns one code per request: 0 applied, 1 stale handle, 2 run
+        no longer active, 3 not a waiting approval, 4 the (slot, step) was
+        already named earlier in this call (only the first is sent)."""
+        self._require_external("decide")
+        cols = [[int(x) for x in c] for c in (slots, gens, steps, verdicts)]
+        n = len(cols[0])
+        if any(len(c) != n for c in cols):
+            raise ValueError("slots, gens, steps and verdicts must match in length")
+        first = {}
+        for i in range(n):           # the kernel assumes distinct (slot, step)
+            first.setdefault((cols[0][i], cols[2][i]), i)
+        keep = sorted(first.values())
+        codes = [4] * n
+        if not keep:
+            return codes
+        k = len(keep)
+        req = torch.tensor([c[i] for c in cols for i in keep],
+                           dtype=torch.int32).to(self.device)
+        out = torch.zeros(k, dtype=torch.uint8, device=self.device)
+        self.ext.wf_decide(req[:k], req[k:2 * k], req[2 * k:3 * k], req[3 * k:],
+                           self.run_life, self.run_gen, self.run_active,
+                           self.n_steps, self.step_kind, self.step_state,
+                           self.hold_counts, out)
+        for i, v in zip(keep, out.cpu().tolist()):
+            codes[i] = v
+        return codes
+
+    def hold_stats(self) -> dict:
+        """Cumulative holds opened / expired / approved / rejected, and the
+        number open after the last tick's scan."""
+        self._require_external("hold_stats")
+        c = self.hold_counts.cpu().tolist()
+        return {"opened": c[0], "expired": c[1], "approved": c[2],
+                "rejected": c[3], "open": int(self.hold_open.cpu()[0])}
+
     def _capture_dynamic(self) -> None:
         """Dynamic mode warms up and captures the tick on the EMPTY table, at
         construction: n calls of tick() then advance the tables by exactly n
@@ -623,6 +777,8 @@ class WorkflowPipeline:
                     self.retry_count, self.admit_count, self.rq_dead]
         if self.event_cap is not None:
             counters.append(self.ev_count)
+        if self.external:
+            counters += [self.hold_counts, self.hold_open]
         saved = [(t, t.clone()) for t in counters]
         for _ in range(2):
             self._tick_device_body()
@@ -720,6 +876,14 @@ class WorkflowPipeline:
                      self.next_ready, self.tick_buf,
                      self.disp_runs, self.disp_steps, self.disp_count,
                      self.appr_runs, self.appr_steps, self.appr_count)
+        if self.external:
+            # open / expire / close approval holds from the run table itself
+            # (the sweep's fresh-hold list is not read in this mode)
+            self.hold_open.zero_()
+            ext.wf_hold_scan(self.step_state, self.n_steps, self.run_life,
+                             self.run_active, self.run_gen, self.tick_buf,
+                             self.hold_ttl, self.hold_mask, self.hold_tick,
+                             self.hold_gen, self.hold_counts, self.hold_open)
 
         # expand into the child arena, spread-routed over the global order
         self.child_count.zero_()
@@ -802,7 +966,7 @@ class WorkflowPipeline:
                       self.run_state, self.wf_counts)
         if self.event_cap is not None:
             self._journal(0)
-        if self._appr_h_count is not None:
+        if self._appr_h_count is not None and not self.external:
             # stream-ordered async D2H of the approval count into pinned
             # memory: the host polls it with event.query() instead of a
             # blocking sync every tick (the grant hop already tolerates a
@@ -854,6 +1018,16 @@ class WorkflowPipeline:
     def tick(self) -> None:
         ext = self.ext
         self._tick += 1
+
+        if self.external:
+            # no host hop: holds wait in the tables for decide(). Nothing is
+            # granted, drained or polled here.
+            if self.device.type == "cuda" and self.world == 1 and bool(self._wf_graph):
+                self._wf_graph.replay()
+            else:
+                self._tick_device_body()
+            self._refresh_order()
+            return
 
         # a drain deferred from last tick (its D2H event was still in
         # flight) MUST land before this tick's body overwrites the approval

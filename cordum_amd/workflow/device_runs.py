@@ -13,6 +13,12 @@ device's step-transition records into `StepEvent`s keyed by run id, per-step
 `STEP_*` statuses, and, given a `WorkflowStore`, the timeline events and run
 records the API serves.
 
+On a pipeline with `approvals="external"` the table serves approval gates as
+the host engine's `approve_step` does: `approvals()` lists the holds that
+wait for a decision, `approve()` / `reject()` settle one by run id and step
+id, and `approval_ttl_sec` at registration lets holds expire (an expired hold
+shows as `step_rejected`).
+
 Wiring an API route to this table, and result / output materialisation, are
 not done here.
 """
@@ -87,6 +93,17 @@ class StepEvent(NamedTuple):
     between_ticks: bool
 
 
+class PendingApproval(NamedTuple):
+    """One approval hold that waits for a decision. `since_tick` is the device
+    tick the hold opened in, `expires_tick` the tick whose scan fails it if it
+    is still undecided (None: it never expires)."""
+    run_id: str
+    step: int
+    step_id: str
+    since_tick: int
+    expires_tick: Optional[int]
+
+
 def timeline_of(kind: int, to_state: int) -> Tuple[str, str, Dict[str, Any]]:
     """(timeline event type, step status, extra data) of a transition into
     `to_state` of a step of `kind`: the host engine's event names where it
@@ -125,7 +142,8 @@ def _steps_of(workflow: Any) -> List[Step]:
 
 
 def dag_from_workflow(workflow: Any, items_len: int,
-                      tick_seconds: float = 1.0) -> Optional[DagSpec]:
+                      tick_seconds: float = 1.0,
+                      approval_ttl_sec: float = 0.0) -> Optional[DagSpec]:
     """Lower a workflow (a `Workflow`, or its `{"steps": {id: step}}` dict
     form) to a device `DagSpec`; steps are indexed in `workflow.steps` order.
     Returns None when the workflow cannot run on the device, and the caller
@@ -133,8 +151,11 @@ def dag_from_workflow(workflow: Any, items_len: int,
     worker / approval / delay, a `condition` expression, `delay_until`,
     `on_error`, a per-step `retry` block, a dependency on a later or unknown
     step, or a `for_each` over no items (the device cannot complete a step
-    with nothing to emit)."""
+    with nothing to emit). `approval_ttl_sec` > 0 gives every approval step
+    that expiry, rounded up to ticks (it needs a pipeline with
+    approvals="external"); 0 lowers approvals without one."""
     steps = _steps_of(workflow)
+    ttl = max(0, int(math.ceil(approval_ttl_sec / tick_seconds)))
     if len(steps) > 64:
         return None
     index = {st.id: i for i, st in enumerate(steps)}
@@ -159,7 +180,7 @@ def dag_from_workflow(workflow: Any, items_len: int,
             else:
                 specs.append(StepSpec(WFK_WORKER, deps=deps))
         elif st.type == "approval":
-            specs.append(StepSpec(WFK_APPROVAL, deps=deps))
+            specs.append(StepSpec(WFK_APPROVAL, deps=deps, ttl_ticks=ttl))
         elif st.type == "delay":
             ticks = int(math.ceil(st.delay_sec / tick_seconds))
             specs.append(StepSpec(WFK_DELAY, deps=deps, delay_ticks=max(0, ticks)))
@@ -182,6 +203,7 @@ class DeviceRunTable:
         self._tmpl_of: Dict[str, int] = {}
         # template id -> (workflow id, step ids or None, step kinds)
         self._tmpl_info: Dict[int, Tuple[str, Optional[List[str]], List[int]]] = {}
+        self._tmpl_ttl: Dict[int, List[int]] = {}    # template id -> hold ttl per step
         self._handle: Dict[str, Tuple[int, int]] = {}
         self._run_of: Dict[Tuple[int, int], str] = {}
         self._queue: Deque[Tuple[str, int, int, int]] = deque()
@@ -217,11 +239,12 @@ class DeviceRunTable:
         return n
 
     def register(self, workflow: Any, items_len: int = 0,
-                 tick_seconds: float = 1.0) -> Optional[int]:
+                 tick_seconds: float = 1.0,
+                 approval_ttl_sec: float = 0.0) -> Optional[int]:
         """Lower `workflow` and add it as a template; returns the template id
         to submit() runs of it with, or None if the workflow must stay on the
         host engine. Events of such runs carry the workflow's step ids."""
-        dag = dag_from_workflow(workflow, items_len, tick_seconds)
+        dag = dag_from_workflow(workflow, items_len, tick_seconds, approval_ttl_sec)
         if dag is None:
             return None
         t = self.pipe.add_template(dag)
@@ -274,6 +297,64 @@ class DeviceRunTable:
         if h is None:
             return False
         return bool(self.pipe.cancel([h[0]], [h[1]])[0])
+
+    # ---- approval gates (pipeline with approvals="external") -----------------
+    def _ttl_of(self, template_id: int) -> List[int]:
+        ttl = self._tmpl_ttl.get(template_id)
+        if ttl is None:
+            row = self.pipe.tmpl_ttl[template_id * 64:template_id * 64 + 64]
+            ttl = self._tmpl_ttl[template_id] = row.cpu().tolist()
+        return ttl
+
+    def approvals(self) -> List[PendingApproval]:
+        """The approval holds that wait for a decision, of the runs this
+        table knows, ascending in (slot, step)."""
+        out = []
+        for slot, gen, step, since in zip(*self.pipe.open_holds()):
+            run_id = self._run_of.get((slot, gen))
+            if run_id is None:
+                continue
+            tmpl = self._tmpl_of[run_id]
+            ids = self._info(tmpl)[1]
+            ttl = self._ttl_of(tmpl)[step]
+            out.append(PendingApproval(
+                run_id, step, ids[step] if ids is not None and step < len(ids) else "",
+                since, since + ttl if ttl > 0 else None))
+        return out
+
+    def _step_index(self, template_id: int, step: Union[str, int]) -> int:
+        _, ids, kinds = self._info(template_id)
+        if isinstance(step, str):
+            if ids is None or step not in ids:
+                raise ValueError("step not found")
+            return ids.index(step)
+        if not 0 <= int(step) < len(kinds):
+            raise ValueError("step not found")
+        return int(step)
+
+    def _decide(self, run_id: str, step: Union[str, int], verdict: int) -> None:
+        h = self._handle.get(run_id)
+        if h is None:
+            for q in self._queue:
+                if q[0] == run_id:        # not admitted yet: nothing waits
+                    self._step_index(q[1], step)
+                    raise ValueError("step not waiting")
+            raise KeyError(run_id)
+        s = self._step_index(self._tmpl_of[run_id], step)
+        if self.pipe.decide([h[0]], [h[1]], [s], [verdict])[0] != 0:
+            raise ValueError("step not waiting")
+
+    def approve(self, run_id: str, step: Union[str, int]) -> None:
+        """Approve a waiting approval step, named by step id or index. As the
+        host engine's approve_step: KeyError for an unknown run, ValueError
+        "step not found" / "step not waiting" otherwise. The run goes on in
+        the next tick."""
+        self._decide(run_id, step, 1)
+
+    def reject(self, run_id: str, step: Union[str, int]) -> None:
+        """Reject a waiting approval step: the step fails, and the run with
+        it, in the next tick. Errors as approve()."""
+        self._decide(run_id, step, 0)
 
     def _drain_events(self) -> None:
         """Journal records -> StepEvents (and the store). Records of a (slot,

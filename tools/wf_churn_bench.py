@@ -24,8 +24,20 @@ poll() drains the journal every tick. It reports runs/s, events/s, the
 table size (life bytes, plus generations, states and shadow of the rows that
 are not FREE, plus the records written).
 
+With --approvals a further mode joins the alternation: the same churn as the
+dynamic window on a pipeline with approvals="external", where every tick
+`open_holds()` lists the waiting approvals and `decide()` approves all of
+them. It reports runs/s, holds/s, `open_holds` and `decide` per call by device
+events, and the bytes one hold scan moves at this table size (a life byte per
+slot; active byte, two generations, the mask and 64 state bytes per row that
+is not FREE; tick and ttl of each continuing hold). It also times the hold
+scan and the journal pass alone, alternating, on tables of --runs rows and of
+--pass-rows rows (quiet: nothing to report; held: one continuing hold / one
+changed step in every row).
+
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --events
+    python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --approvals
 """
 import argparse
 import json
@@ -54,6 +66,12 @@ def main() -> int:
     ap.add_argument("--events", type=int, nargs="?", const=0, default=None, metavar="CAP",
                     help="also run the churn with the step journal on "
                          "(CAP records; default 2 * runs * 64)")
+    ap.add_argument("--approvals", action="store_true",
+                    help="also run the churn with externally decided approvals "
+                         "(open_holds + approve everything, every tick)")
+    ap.add_argument("--pass-rows", type=int, default=1 << 20,
+                    help="second table size for the scan / journal pass timings "
+                         "(0: no pass timings, for a kernel trace of the churn alone)")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="rehearse the host logic on the reference backend (no timings)")
     args = ap.parse_args()
@@ -160,6 +178,81 @@ def main() -> int:
             sync()
             return ok, time.perf_counter() - t0
 
+    # ---- dynamic mode with externally decided approvals --------------------
+    ap_window = None
+    if args.approvals:
+        exp = WorkflowPipeline(dags=[dag], dynamic_capacity=args.runs,
+                               approvals="external", **common)
+        t_holds, t_decide = Timer(), Timer()
+        ap_live = [0]
+        n_holds = [0]
+        got, _ = exp.admit([0] * args.runs)
+        ap_live[0] = sum(1 for s in got if s >= 0)
+        assert ap_live[0] == args.runs
+
+        def ap_window(n_ticks):
+            ok = 0
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(n_ticks):
+                exp.tick()
+                slots, gens, steps, _ = t_holds(exp.open_holds)
+                if slots:
+                    codes = t_decide(exp.decide, slots, gens, steps, [1] * len(slots))
+                    assert not any(codes)
+                    n_holds[0] += len(slots)
+                _, _, states = exp.drain_completed()
+                ok += sum(1 for s in states if s == WFS_SUCCEEDED)
+                ap_live[0] -= len(states)
+                want = args.runs - ap_live[0]
+                if want:
+                    got, _ = exp.admit([0] * want)
+                    ap_live[0] += sum(1 for s in got if s >= 0)
+            sync()
+            return ok, time.perf_counter() - t0
+
+    def pass_times(NR, held, reps=15):
+        """Hold scan and journal pass alone on an all-LIVE table of NR rows,
+        alternating, one device-event pair per launch; µs, median (min..max).
+        Quiet: nothing waits and nothing changed. Held: every row has one
+        continuing hold (scan), one changed step (journal)."""
+        ext, d = dyn.ext, device
+        st = torch.full((NR * 64,), WFS_SUCCEEDED, dtype=torch.uint8, device=d)
+        ones8 = torch.ones(NR, dtype=torch.uint8, device=d)
+        gen = torch.ones(NR, dtype=torch.int32, device=d)
+        hgen, sgen = gen.clone(), gen.clone()      # hold / shadow generations
+        ns =torch.full((NR,), 4, dtype=torch.uint8, device=d)
+        tickb = torch.tensor([5], dtype=torch.int32, device=d)
+        ttl = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+        htick = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+        mask = torch.zeros(NR, dtype=torch.int64, device=d)
+        counts = torch.zeros(4, dtype=torch.int64, device=d)
+        hopen = torch.zeros(1, dtype=torch.int32, device=d)
+        if held:
+            st.view(NR, 64)[:, 1] = 2              # WFS_WAITING
+            ttl.view(NR, 64)[:, 1] = 1 << 30
+            mask.fill_(2)
+        shadow = st.clone()
+        rec = torch.zeros(4 * (NR + 1024), dtype=torch.int32, device=d)
+        cnt = torch.zeros(1, dtype=torch.int32, device=d)
+        scan_t, jour_t = Timer(), Timer()
+        for i in range(reps + 3):
+            if held:
+                shadow.view(NR, 64)[:, 1] = 0      # one change per row, again
+                cnt.zero_()
+            hopen.zero_()
+            scan_t(ext.wf_hold_scan, st, ns, ones8, ones8, gen, tickb, ttl, mask,
+                   htick, hgen, counts, hopen)
+            jour_t(ext.wf_journal, st, ones8, gen, tickb, 0, shadow, sgen, rec, cnt)
+            sync()
+            if i < 3:                              # warm-up launches
+                scan_t.take_ms(), jour_t.take_ms()
+        if not use_gpu:
+            return None
+        return {"rows": NR, "case": "held" if held else "quiet",
+                "scan_us": spread([1000 * x for x in scan_t.take_ms()]),
+                "journal_us": spread([1000 * x for x in jour_t.take_ms()])}
+
     # ---- baseline: readmit continuous mode ---------------------------------
     sta = WorkflowPipeline(dags=[dag], replicate=args.runs, **common)
     sta.reset_runs()
@@ -178,26 +271,39 @@ def main() -> int:
     modes = [("dynamic", dyn_window), ("readmit", sta_window)]
     if ev_window is not None:
         modes.insert(1, ("events", ev_window))
+    if ap_window is not None:
+        modes.insert(1, ("approvals", ap_window))
     for _, window in modes:
         window(args.warmup)
     t_admit.take_ms(), t_drain.take_ms(), t_readmit.take_ms()
+    if ap_window is not None:
+        t_holds.take_ms(), t_decide.take_ms()
 
     rate = {name: [] for name, _ in modes}
     tick_ms = {name: [] for name, _ in modes}
     ev_rate = []
+    hold_rate = []
     call_ms = {"admit": [], "drain_completed": [], "readmit_succeeded": []}
+    timers = [("admit", t_admit), ("drain_completed", t_drain),
+              ("readmit_succeeded", t_readmit)]
+    if ap_window is not None:
+        call_ms.update(open_holds=[], decide=[])
+        timers += [("open_holds", t_holds), ("decide", t_decide)]
     for _ in range(args.repeats):
         for name, window in modes:
             if name == "events":
                 n_events[0] = 0
+            if name == "approvals":
+                n_holds[0] = 0
             ok, dt = window(args.ticks)
             rate[name].append(ok / dt)
             tick_ms[name].append(dt / args.ticks * 1000.0)
             if name == "events":
                 ev_rate.append(n_events[0] / dt)
+            if name == "approvals":
+                hold_rate.append(n_holds[0] / dt)
         # per-call medians of this repeat
-        for key, timer in (("admit", t_admit), ("drain_completed", t_drain),
-                           ("readmit_succeeded", t_readmit)):
+        for key, timer in timers:
             ms = timer.take_ms()
             if ms:
                 call_ms[key].append(statistics.median(ms))
@@ -234,6 +340,27 @@ def main() -> int:
             "events_per_tick": round(per_tick, 1),
             "journal_bytes_per_pass": int(pass_bytes),
             "graph": bool(evp._wf_graph),
+        }
+    if ap_window is not None:
+        per_tick = statistics.median(hold_rate) * statistics.median(tick_ms["approvals"]) / 1000.0
+        # one scan: a life byte per slot; active byte, generation + hold
+        # generation, the mask word and 64 state bytes per row that is not
+        # FREE (the table is held full); a fresh hold writes its tick and the
+        # mask, a continuing one reads its ttl (and its tick when ttl > 0)
+        scan_bytes = args.runs * (1 + 1 + 4 + 4 + 8 + 64) + (4 + 8) * per_tick
+        out["approvals"] = {
+            "hold_cap": exp.hold_cap,
+            "runs_per_s": spread(rate["approvals"]),
+            "holds_per_s": spread(hold_rate),
+            "approvals_over_dynamic": round(
+                statistics.median(rate["approvals"]) / max(1e-9, statistics.median(rate["dynamic"])), 3),
+            "holds_per_tick": round(per_tick, 1),
+            "scan_bytes_per_pass": int(scan_bytes),
+            "hold_stats": exp.hold_stats(),
+            "graph": bool(exp._wf_graph),
+            "pass_times": [pass_times(n, held) for n in
+                           ((args.runs, args.pass_rows) if use_gpu else (64,))
+                           for held in (False, True)] if args.pass_rows else [],
         }
     print(json.dumps(out))
     return 0
