@@ -1445,6 +1445,161 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K3-WF per-step retry / backoff / timeout policy: wf_settle
+// ---------------------------------------------------------------------------
+// With a per-step policy the tick launches wf_settle in place of the pair
+// wf_timeout_scan + wf_commit. Both of those act on index i only, so running
+// them back to back per step is the same computation; what differs is where
+// the constants come from. The policy is held per template (templates are
+// append-only), and run_tmpl[r] names the template of the row's occupant:
+//   tmpl_policy[(t*64+s)*4 ..] = (max_retries, backoff_ticks, cap_ticks,
+//                                 multiplier_q8), one 16-byte record per step
+//   tmpl_timeout[t*64+s]       = ticks after which outstanding children are
+//                                 written off (resolved: never 0, never below
+//                                 the pipeline's cutoff)
+// The host validates the records (wf_pipeline.py); the kernel trusts their
+// ranges and checks only that the template id is inside the table. A row
+// whose id is not is left alone.
+//
+// One deliberate difference from the pair: FREE rows are skipped. With a step
+// timeout longer than the pipeline cutoff wf_retire can free a row that still
+// holds a DISPATCHED step with children counted outstanding; its bytes belong
+// to nobody and the next admission overwrites them.
+//
+// backoff(k), integers only (16.16 fixed point, multiplier in 8.8); the
+// oracle (reference.wf_backoff_ref) uses the same arithmetic:
+//   limit = (cap_ticks > 0 ? cap_ticks : 1<<20) << 16
+//   d = min(backoff_ticks << 16, limit)
+//   min(k-1, 63) times, stopping once d == limit: d = min((d*mult_q8) >> 8, limit)
+//   backoff = (d + 65535) >> 16
+// d <= 2^36 and mult_q8 < 2^16 for validated records, so d*mult_q8 < 2^52.
+__device__ __forceinline__ int wf_backoff_ticks(int k, int backoff_ticks, int cap_ticks,
+                                                int mult_q8)
+{
+    const unsigned long long limit =
+        (unsigned long long)(cap_ticks > 0 ? cap_ticks : (1 << 20)) << 16;
+    unsigned long long d = min((unsigned long long)(unsigned)backoff_ticks << 16, limit);
+    const int n = min(k - 1, 63);
+#pragma unroll 1
+    for (int i = 0; i < n && d != limit; ++i)
+        d = min((d * (unsigned long long)(unsigned)mult_q8) >> 8, limit);
+    return (int)((d + 65535ull) >> 16);
+}
+
+// Layout as the journal and the hold scan: 4 lanes per row, 16 steps (one
+// 16-byte state load) per lane, 16 rows per wave, 64 rows per block. A FREE
+// row costs its life byte. A wave with no DISPATCHED byte does nothing more
+// after the loads and writes nothing. Only a lane that holds a DISPATCHED
+// byte reads run_tmpl and the counter columns of those steps, and only a step
+// with failed children and none outstanding reads its policy record. A lane
+// owns its 16 state bytes and stores them back, as one 16-byte store, only if
+// one changed. timeout_count / retry_count: summed per block, at most one
+// atomic add per block and counter.
+__global__ __launch_bounds__(BLOCK) void wf_settle_kernel(
+    unsigned char* __restrict__ step_state,         // [NR*64]
+    int* __restrict__ step_attempts,                // [NR*64]
+    int* __restrict__ children_todo,
+    int* __restrict__ children_out,
+    int* __restrict__ children_fail,
+    const int* __restrict__ max_parallel,
+    int* __restrict__ next_ready,
+    const int* __restrict__ dispatch_tick,          // [NR*64]
+    const unsigned char* __restrict__ run_life,     // [NR]
+    const int* __restrict__ run_tmpl,               // [NR]
+    const int4* __restrict__ tmpl_policy,           // [TC*64]
+    const int* __restrict__ tmpl_timeout,           // [TC*64]
+    const int* __restrict__ tick_p,
+    unsigned long long* __restrict__ timeout_count,
+    unsigned long long* __restrict__ retry_count,
+    int NR, int TC)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int r = t >> 2;                           // 4 lanes per row
+    const int q = t & 3;                            // steps 16q .. 16q+15
+    const bool live = r < NR && run_life[r] != WFL_FREE;
+    const size_t off = (size_t)r * 64 + (size_t)q * 16;
+    uint4 st = make_uint4(0u, 0u, 0u, 0u);          // WFS_PENDING == 0
+    if (live) st = *reinterpret_cast<const uint4*>(step_state + off);
+    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
+    unsigned disp = 0u;                             // bit j: step 16q+j is DISPATCHED
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        disp |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_DISPATCHED) << j;
+
+    unsigned long long lost_sum = 0ull, retry_sum = 0ull;
+    if (__any(disp != 0u)) {                        // wave-uniform
+        if (disp != 0u) {
+            const int tmpl = run_tmpl[r];
+            if (tmpl < 0 || tmpl >= TC) disp = 0u;  // no such template: leave the row
+            const size_t pol = (size_t)tmpl * 64 + (size_t)q * 16;
+            const int tick = *tick_p;
+            unsigned nw[4] = {sw[0], sw[1], sw[2], sw[3]};
+#pragma unroll 1
+            for (unsigned f = disp; f != 0u; f &= f - 1u) {
+                const int j = __ffs((int)f) - 1;
+                const size_t i = off + j;
+                int out = children_out[i];
+                int fail = children_fail[i];
+                const int fail0 = fail;
+                // 1. timeout: the remainder is lost and counts as failed
+                if (out > 0 && dispatch_tick[i] <= tick - tmpl_timeout[pol + j]) {
+                    fail += out;
+                    lost_sum += (unsigned long long)out;
+                    out = 0;
+                    children_out[i] = 0;
+                }
+                // 2. commit
+                int next = WFS_DISPATCHED;
+                if (out != 0) {
+                    // window slide: work left and room in the window
+                    const int mp = max_parallel[i];
+                    if (children_todo[i] > 0 && (mp == 0 || out < mp)) next = WFS_PENDING;
+                } else if (fail > 0) {
+                    const int4 p = tmpl_policy[pol + j];  // max_retries, backoff, cap, mult
+                    const int att = step_attempts[i];
+                    if (att < p.x) {
+                        step_attempts[i] = att + 1;
+                        children_todo[i] += fail;   // only failed children re-run
+                        next_ready[i] = tick + wf_backoff_ticks(att + 1, p.y, p.z, p.w);
+                        retry_sum += (unsigned long long)fail;
+                        fail = 0;
+                        next = WFS_PENDING;
+                    } else {
+                        next = WFS_FAILED;
+                    }
+                } else {
+                    next = children_todo[i] > 0 ? WFS_PENDING : WFS_SUCCEEDED;
+                }
+                if (fail != fail0) children_fail[i] = fail;
+                const int sft = (j & 3) * 8;
+                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | ((unsigned)next << sft);
+            }
+            if (nw[0] != sw[0] || nw[1] != sw[1] || nw[2] != sw[2] || nw[3] != sw[3])
+                *reinterpret_cast<uint4*>(step_state + off) =
+                    make_uint4(nw[0], nw[1], nw[2], nw[3]);
+        }
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            lost_sum += __shfl_xor(lost_sum, d, WAVE);
+            retry_sum += __shfl_xor(retry_sum, d, WAVE);
+        }
+    }
+    // one add per counter and block, not per wave (see wf_hold_scan)
+    __shared__ unsigned long long part[2][BLOCK / WAVE];
+    if (threadIdx.x % WAVE == 0) {
+        part[0][threadIdx.x / WAVE] = lost_sum;
+        part[1][threadIdx.x / WAVE] = retry_sum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long nl = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        const unsigned long long nr = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        if (nl) atomicAdd(timeout_count, nl);
+        if (nr) atomicAdd(retry_count, nr);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // K3-WF externally decided approvals: hold scan / hold list / decide
 // ---------------------------------------------------------------------------
 // With approvals decided from outside, an APPROVAL step that wf_sweep set
@@ -3499,6 +3654,52 @@ void wf_hold_scan(torch::Tensor step_state, torch::Tensor n_steps, torch::Tensor
         hold_open.data_ptr<int>(), (int)NR);
 }
 
+// one settle pass on the current stream (inside the tick, in place of
+// wf_timeout_scan + wf_commit); tmpl_policy is [TC*64*4], tmpl_timeout [TC*64]
+void wf_settle(torch::Tensor step_state, torch::Tensor step_attempts,
+               torch::Tensor children_todo, torch::Tensor children_out,
+               torch::Tensor children_fail, torch::Tensor max_parallel,
+               torch::Tensor next_ready, torch::Tensor dispatch_tick,
+               torch::Tensor run_life, torch::Tensor run_tmpl,
+               torch::Tensor tmpl_policy, torch::Tensor tmpl_timeout,
+               torch::Tensor tick, torch::Tensor timeout_count, torch::Tensor retry_count)
+{
+    const int64_t NR = run_life.numel();
+    const int64_t TC = tmpl_timeout.numel() / 64;
+    if (NR <= 0) return;
+    TORCH_CHECK(step_state.numel() == NR * 64 && step_attempts.numel() == NR * 64
+                && children_todo.numel() == NR * 64 && children_out.numel() == NR * 64
+                && children_fail.numel() == NR * 64 && max_parallel.numel() == NR * 64
+                && next_ready.numel() == NR * 64 && dispatch_tick.numel() == NR * 64
+                && run_tmpl.numel() == NR, "wf_settle: table sizes disagree");
+    TORCH_CHECK(TC >= 1 && tmpl_timeout.numel() == TC * 64
+                && tmpl_policy.numel() == TC * 64 * 4 && TC * 64 <= (int64_t)INT_MAX,
+                "wf_settle: policy tables need TC*64*4 and TC*64 words, TC >= 1");
+    TORCH_CHECK(tick.numel() >= 1 && timeout_count.numel() >= 1 && retry_count.numel() >= 1,
+                "wf_settle: tick and counters need one word each");
+    TORCH_CHECK(step_state.is_contiguous() && step_attempts.is_contiguous()
+                && children_todo.is_contiguous() && children_out.is_contiguous()
+                && children_fail.is_contiguous() && max_parallel.is_contiguous()
+                && next_ready.is_contiguous() && dispatch_tick.is_contiguous()
+                && run_tmpl.is_contiguous() && tmpl_policy.is_contiguous()
+                && tmpl_timeout.is_contiguous(), "wf_settle: tables must be contiguous");
+    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_settle: table too large");
+    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
+                && (uintptr_t)tmpl_policy.data_ptr<int>() % 16 == 0,
+                "wf_settle: states and policy records must be 16-byte aligned");
+    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(wf_settle_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        step_state.data_ptr<uint8_t>(), step_attempts.data_ptr<int>(),
+        children_todo.data_ptr<int>(), children_out.data_ptr<int>(),
+        children_fail.data_ptr<int>(), max_parallel.data_ptr<int>(),
+        next_ready.data_ptr<int>(), dispatch_tick.data_ptr<int>(),
+        run_life.data_ptr<uint8_t>(), run_tmpl.data_ptr<int>(),
+        reinterpret_cast<const int4*>(tmpl_policy.data_ptr<int>()),
+        tmpl_timeout.data_ptr<int>(), tick.data_ptr<int>(),
+        (unsigned long long*)timeout_count.data_ptr<int64_t>(),
+        (unsigned long long*)retry_count.data_ptr<int64_t>(), (int)NR, (int)TC);
+}
+
 // one page of open holds, three launches on the current stream. list is
 // [count, pad x3 | cap records of 4 words]; list_mask / blk_scan are
 // caller-owned workspaces ([NR] int64, [nblk+1] int32, nblk = ceil(NR/256))
@@ -3854,6 +4055,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_retire", &wf_retire, "K3-WF completion records + quiescent slot release");
     m.def("wf_journal", &wf_journal, "K3-WF step-transition journal pass (observer)");
     m.def("wf_hold_scan", &wf_hold_scan, "K3-WF approval hold scan (open / expire / close holds)");
+    m.def("wf_settle", &wf_settle, "K3-WF per-step-policy timeout + commit pass (replaces the scan/commit pair)");
     m.def("wf_hold_list", &wf_hold_list, "K3-WF ordered page of open approval holds");
     m.def("wf_decide", &wf_decide, "K3-WF generation-checked approval decisions");
     m.def("materialize_rq_payload", &materialize_rq_payload, "copy requeued payload rows into the rq arena");

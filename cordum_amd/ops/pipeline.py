@@ -354,6 +354,11 @@ class _RefOps:
 
         wf_hold_scan_ref(*a)
 
+    def wf_settle(self, *a):
+        from .reference import wf_settle_ref
+
+        wf_settle_ref(*a)
+
     def wf_hold_list(self, st, rl, ra, rg, hm, ht, hg, cursor, lm, bs, out):
         from .reference import wf_hold_list_ref
 

@@ -812,3 +812,70 @@ def wf_decide_ref(req_slot, req_gen, req_step, req_verdict, run_life, run_gen,
             step_state[slot * 64 + step] = WFS_SUCCEEDED if yes else WFS_FAILED
             hold_counts[2 if yes else 3] += 1
             out_code[i] = 0
+
+
+# -- K3-WF per-step retry / backoff / timeout policy (wf_settle) ----------------
+def wf_backoff_ref(k: int, backoff_ticks: int, cap_ticks: int, multiplier_q8: int) -> int:
+    """Ticks to wait before attempt k + 1 (k >= 1 failures so far): integers
+    only, 16.16 fixed point with an 8.8 multiplier, the kernel's arithmetic.
+    cap_ticks 0 means no cap; the delay then saturates at 2^20 ticks."""
+    limit = (cap_ticks if cap_ticks > 0 else 1 << 20) << 16
+    d = min(backoff_ticks << 16, limit)
+    for _ in range(min(k - 1, 63)):
+        if d == limit:
+            break
+        d = min((d * multiplier_q8) >> 8, limit)
+    return (d + 65535) >> 16
+
+
+def wf_settle_ref(step_state, step_attempts, children_todo, children_out,
+                  children_fail, max_parallel, next_ready, dispatch_tick,
+                  run_life, run_tmpl, tmpl_policy, tmpl_timeout, tick,
+                  timeout_count, retry_count):
+    """wf_timeout_scan followed by wf_commit, per DISPATCHED step of every row
+    that is not FREE, with the step's own constants: its record
+    tmpl_policy[(t*64+s)*4:+4] = (max_retries, backoff_ticks, cap_ticks,
+    multiplier_q8) and tmpl_timeout[t*64+s], t = run_tmpl[row]. A row whose
+    template id is outside the table is left alone."""
+    NR = int(run_life.shape[0])
+    TC = int(tmpl_timeout.shape[0]) // 64
+    now = int(tick[0])
+    st = step_state.view(NR, 64)
+    rows = torch.nonzero((run_life[:NR] != WFL_FREE)
+                         & (st == WFS_DISPATCHED).any(dim=1)).flatten().tolist()
+    lost_sum = retry_sum = 0
+    for r in rows:
+        t = int(run_tmpl[r])
+        if not 0 <= t < TC:
+            continue
+        for s in torch.nonzero(st[r] == WFS_DISPATCHED).flatten().tolist():
+            i, p = r * 64 + s, t * 64 + s
+            out, fail = int(children_out[i]), int(children_fail[i])
+            if out > 0 and int(dispatch_tick[i]) <= now - int(tmpl_timeout[p]):
+                fail += out
+                lost_sum += out
+                out = 0
+                children_out[i] = 0
+                children_fail[i] = fail
+            if out != 0:
+                mp = int(max_parallel[i])
+                if int(children_todo[i]) > 0 and (mp == 0 or out < mp):
+                    step_state[i] = WFS_PENDING
+            elif fail > 0:
+                max_retries, backoff, cap, mult = tmpl_policy[4 * p:4 * p + 4].tolist()
+                att = int(step_attempts[i])
+                if att < max_retries:
+                    step_attempts[i] = att + 1
+                    children_todo[i] += fail
+                    children_fail[i] = 0
+                    next_ready[i] = now + wf_backoff_ref(att + 1, backoff, cap, mult)
+                    step_state[i] = WFS_PENDING
+                    retry_sum += fail
+                else:
+                    step_state[i] = WFS_FAILED
+            elif int(children_todo[i]) > 0:
+                step_state[i] = WFS_PENDING
+            else:
+                step_state[i] = WFS_SUCCEEDED
+    timeout_count[0] += lost_sum
+    retry_count[0] += retry_sum

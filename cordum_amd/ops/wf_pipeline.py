@@ -50,6 +50,13 @@ host hop above is gone, a hold stays WAITING until decide() names it by
 `ttl_ticks` lets a hold expire (see "externally decided approvals" below).
 One more kernel (wf_hold_scan) follows the sweep. With the default
 `approvals="auto"` nothing is allocated and the tick is unchanged.
+
+With `step_policy=True` dynamic mode takes retry, backoff and timeout per
+step (`StepSpec.retry`, `StepSpec.timeout_ticks`) instead of per pipeline:
+one kernel (wf_settle) stands in for the pair wf_timeout_scan + wf_commit and
+reads each step's constants from its template (see "per-step policy" below).
+With the default `step_policy=False` nothing is allocated and the tick is
+unchanged.
 """
 from __future__ import annotations
 
@@ -71,6 +78,19 @@ WFK_WORKER, WFK_FOR_EACH, WFK_APPROVAL, WFK_CONDITION, WFK_DELAY = 0, 1, 2, 3, 4
 
 
 @dataclass
+class RetrySpec:
+    """Retry policy of one step (pipeline with step_policy): after failure k
+    (k = 1 .. max_retries) the step waits backoff_ticks * (multiplier_q8 /
+    256)^(k-1) ticks, rounded up and capped at cap_ticks (0 = no cap; the
+    delay then saturates at 2^20 ticks). The defaults are the constants of a
+    pipeline without step_policy: 2, 4, 8, 16, 16, ..."""
+    max_retries: int
+    backoff_ticks: int = 2
+    multiplier_q8: int = 512
+    cap_ticks: int = 16
+
+
+@dataclass
 class StepSpec:
     kind: int
     deps: Sequence[int] = ()
@@ -79,6 +99,10 @@ class StepSpec:
     cond: bool = True        # CONDITION value (pre-evaluated)
     max_parallel: int = 0    # for_each window (0 = unlimited)
     ttl_ticks: int = 0       # APPROVAL hold expiry (0 = never; external approvals)
+    # step_policy pipelines: None = the pipeline's max_retries with the stock
+    # backoff; 0 = the pipeline's timeout_cutoff
+    retry: Optional[RetrySpec] = None
+    timeout_ticks: int = 0   # ticks until lost children are written off
 
 
 @dataclass
@@ -142,9 +166,21 @@ class WorkflowPipeline:
         # hold_cap is the page size of open_holds()
         approvals: str = "auto",
         hold_cap: Optional[int] = None,
+        # dynamic mode only: retry / backoff / timeout per step, read from the
+        # template by wf_settle (see "per-step policy")
+        step_policy: bool = False,
     ):
         if approvals not in ("auto", "external"):
             raise ValueError("approvals must be 'auto' or 'external'")
+        self.step_policy = bool(step_policy)
+        if self.step_policy and dynamic_capacity is None:
+            raise ValueError("step_policy needs dynamic_capacity: the policy is "
+                             "held per template")
+        self.max_retries = max_retries
+        self.timeout_cutoff = timeout_cutoff
+        for dg in dags:
+            for s in dg.steps:
+                self._check_policy(s)
         self.external = approvals == "external"
         if self.external and dynamic_capacity is None:
             raise ValueError("approvals='external' needs dynamic_capacity: a "
@@ -175,8 +211,6 @@ class WorkflowPipeline:
         self.W = payload_words
         self.fail_ppt = fail_ppt
         self.drop_ppt = drop_ppt
-        self.max_retries = max_retries
-        self.timeout_cutoff = timeout_cutoff
         self.approval_verdict = approval_verdict
         if replicate is not None:
             assert len(dags) == 1
@@ -446,9 +480,74 @@ class WorkflowPipeline:
                                          device=d)
             self._hold_list_mask = torch.zeros(NR, dtype=torch.int64, device=d)
             self._hold_blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
+        if self.step_policy:
+            # policy tables (see "per-step policy"): every record starts as
+            # the pipeline's own constants, so a row can never read a zero
+            # timeout. run_tmpl has one spare word past the table: admit()
+            # sends the template ids of refused requests there.
+            if not 0 <= int(self.max_retries) <= 32767:
+                raise ValueError("step_policy needs max_retries in 0..32767")
+            if int(self.timeout_cutoff) < 1:
+                raise ValueError("step_policy needs timeout_cutoff >= 1")
+            stock = RetrySpec(int(self.max_retries))
+            self.tmpl_policy = torch.tensor(
+                [stock.max_retries, stock.backoff_ticks, stock.cap_ticks,
+                 stock.multiplier_q8], dtype=torch.int32).repeat(TC * 64).to(d)
+            self.tmpl_timeout = torch.full((TC * 64,), int(self.timeout_cutoff),
+                                           dtype=torch.int32, device=d)
+            self._run_tmpl_buf = torch.zeros(NR + 1, dtype=torch.int32, device=d)
+            self.run_tmpl = self._run_tmpl_buf[:NR]
         for dag in templates:
             self.add_template(dag)
         self._capture_dynamic()
+
+    # ---- per-step policy (dynamic mode, step_policy=True) --------------------
+    # Retry, backoff and timeout are properties of a step, held per template
+    # (templates are append-only) and not per run:
+    #   tmpl_policy  [template_cap*64*4]  one 16-byte record per step:
+    #                (max_retries, backoff_ticks, cap_ticks, multiplier_q8)
+    #   tmpl_timeout [template_cap*64]    ticks until lost children are written
+    #                off, resolved (never 0, never below timeout_cutoff)
+    #   run_tmpl     [NR]                 the template of the row's occupant,
+    #                written by admit(); a row is admitted only there, so it
+    #                holds for as long as the row is LIVE or DRAINING
+    # wf_settle does per DISPATCHED step what wf_timeout_scan and then
+    # wf_commit do, with these constants, and replaces both in the tick. A
+    # step without a RetrySpec gets the pipeline's max_retries with the stock
+    # 2 / x2 / cap 16, a step without timeout_ticks the pipeline's cutoff, so
+    # a pipeline with no annotated step computes what it computes without
+    # step_policy.
+    #
+    # A step's timeout can only lengthen the wait: timeout_cutoff is what
+    # guarantees that a child parked in the requeue ring is never declared
+    # lost and applied afterwards, and wf_retire keeps releasing rows by it.
+    # A FREE row can therefore hold a DISPATCHED step whose longer timeout
+    # has not run out; wf_settle skips FREE rows.
+    _POLICY_KINDS = (WFK_WORKER, WFK_FOR_EACH)
+
+    def _check_policy(self, spec: StepSpec) -> None:
+        if spec.retry is None and not spec.timeout_ticks:
+            return
+        if not self.step_policy:
+            raise ValueError("retry / timeout_ticks need step_policy=True")
+        if spec.kind not in self._POLICY_KINDS:
+            raise ValueError("retry / timeout_ticks belong on a step that emits "
+                             "children (WORKER, FOR_EACH)")
+        t = int(spec.timeout_ticks)
+        if t < 0 or 0 < t < self.timeout_cutoff:
+            raise ValueError(
+                f"timeout_ticks {t} is below timeout_cutoff {self.timeout_cutoff}: a "
+                "child parked in the requeue ring could be declared lost and "
+                "then applied")
+        if t > (1 << 30):
+            raise ValueError("timeout_ticks must stay below 2^30")
+        r = spec.retry
+        if r is None:
+            return
+        for name, lo, hi in (("max_retries", 0, 32767), ("backoff_ticks", 1, 1 << 20),
+                             ("multiplier_q8", 256, 65535), ("cap_ticks", 0, 1 << 20)):
+            if not lo <= int(getattr(r, name)) <= hi:
+                raise ValueError(f"{name} {getattr(r, name)} outside {lo}..{hi}")
 
     def _require_dynamic(self, dynamic: bool, what: str) -> None:
         if self.dynamic != dynamic:
@@ -474,6 +573,7 @@ class WorkflowPipeline:
                 if spec.kind != WFK_APPROVAL or spec.ttl_ticks < 0:
                     raise ValueError("ttl_ticks is a positive tick count on an "
                                      "APPROVAL step")
+            self._check_policy(spec)
         deps = torch.zeros(64, dtype=torch.int64)
         kinds = torch.zeros(64, dtype=torch.uint8)
         todo = torch.zeros(64, dtype=torch.int32)
@@ -507,6 +607,19 @@ class WorkflowPipeline:
                                + [0] * (64 - len(dag.steps)), dtype=torch.int32)
             self.tmpl_ttl[row].copy_(ttl)
             self._any_ttl = self._any_ttl or bool(ttl.any())
+        if self.step_policy:
+            stock = RetrySpec(int(self.max_retries))
+            pol, tmo = [], []
+            for s in range(64):
+                sp = dag.steps[s] if s < len(dag.steps) else None
+                r = sp.retry if sp is not None and sp.retry is not None else stock
+                pol += [int(r.max_retries), int(r.backoff_ticks), int(r.cap_ticks),
+                        int(r.multiplier_q8)]
+                tmo.append(int(sp.timeout_ticks) if sp is not None and sp.timeout_ticks
+                           else int(self.timeout_cutoff))
+            self.tmpl_policy[t * 256:t * 256 + 256].copy_(
+                torch.tensor(pol, dtype=torch.int32))
+            self.tmpl_timeout[row].copy_(torch.tensor(tmo, dtype=torch.int32))
         self._tmpl_cond.append(cbits - (1 << 64) if cbits >= (1 << 63) else cbits)
         self.n_templates = t + 1
         return t
@@ -552,6 +665,12 @@ class WorkflowPipeline:
             self.run_state, self.run_active, self.run_life, self.run_gen,
             self.tick_buf, self._free_mask, self._blk_scan,
             out[:n], out[n:], self.admit_count)
+        if self.step_policy:
+            # run_tmpl is a run column wf_admit does not know: one indexed
+            # store of the accepted requests' template ids. A refused request
+            # has slot -1, and -1 mod (NR + 1) = NR is the spare word past the
+            # table, so no mask and no host round trip is needed.
+            self._run_tmpl_buf[torch.remainder(out[:n], self.NR + 1)] = req[2 * n:3 * n]
         if self.external and self._any_ttl:
             # hold_ttl is a run column like max_parallel: the template's row
             # goes into every slot just filled (all zero until a template
@@ -955,13 +1074,23 @@ class WorkflowPipeline:
                           self.rq_prev_tag, self.children_fail, self.children_out)
         # K4-WF: steps whose children were lost (worker crash) time out and
         # the remainder retries with backoff (reconciler.go:88-144)
-        ext.wf_timeout_scan(self.step_state, self.children_out,
-                            self.children_fail, self.dispatch_tick,
-                            self.tick_buf, self.timeout_cutoff, self.timeout_count)
-        ext.wf_commit(self.step_state, self.step_attempts, self.children_todo,
-                      self.children_out, self.children_done, self.children_fail,
-                      self.max_parallel,
-                      self.next_ready, self.tick_buf, self.max_retries, self.retry_count)
+        if self.step_policy:
+            # the same two stages in one pass, with each step's own retry,
+            # backoff and timeout (see "per-step policy")
+            ext.wf_settle(self.step_state, self.step_attempts, self.children_todo,
+                          self.children_out, self.children_fail, self.max_parallel,
+                          self.next_ready, self.dispatch_tick, self.run_life,
+                          self.run_tmpl, self.tmpl_policy, self.tmpl_timeout,
+                          self.tick_buf, self.timeout_count, self.retry_count)
+        else:
+            ext.wf_timeout_scan(self.step_state, self.children_out,
+                                self.children_fail, self.dispatch_tick,
+                                self.tick_buf, self.timeout_cutoff, self.timeout_count)
+            ext.wf_commit(self.step_state, self.step_attempts, self.children_todo,
+                          self.children_out, self.children_done, self.children_fail,
+                          self.max_parallel,
+                          self.next_ready, self.tick_buf, self.max_retries,
+                          self.retry_count)
         ext.wf_status(self.step_state, self.n_steps, self.run_active,
                       self.run_state, self.wf_counts)
         if self.event_cap is not None:

@@ -19,6 +19,10 @@ wait for a decision, `approve()` / `reject()` settle one by run id and step
 id, and `approval_ttl_sec` at registration lets holds expire (an expired hold
 shows as `step_rejected`).
 
+On a pipeline with `step_policy=True` registration also lowers each worker
+step's `retry` block and `timeout_sec` (`lower_retry`, `dag_from_workflow`):
+a step retries as often, and waits as many ticks, as the host engine would.
+
 Wiring an API route to this table, and result / output materialisation, are
 not done here.
 """
@@ -28,8 +32,10 @@ import math
 from collections import deque
 from typing import Any, Deque, Dict, List, NamedTuple, Optional, Tuple, Union
 
+from ..ops.reference import wf_backoff_ref
 from ..ops.wf_pipeline import (
     DagSpec,
+    RetrySpec,
     StepSpec,
     WFK_APPROVAL,
     WFK_CONDITION,
@@ -141,19 +147,72 @@ def _steps_of(workflow: Any) -> List[Step]:
     return out
 
 
+def _ceil_ticks(seconds: float, tick_seconds: float) -> int:
+    return int(math.ceil(seconds / tick_seconds))
+
+
+def lower_retry(step: Step, tick_seconds: float) -> Optional[RetrySpec]:
+    """The device `RetrySpec` of a worker step's `retry` block, or None if
+    the device's integer backoff would not wait what the host engine waits.
+    No block (or max_retries <= 0) is the host's "never retry". The result is
+    proved, not assumed: for every attempt k in 1..max_retries the device
+    formula must give ceil(compute_backoff(step, attempts=k) / tick_seconds)."""
+    from .engine import compute_backoff
+
+    cfg = step.retry
+    if cfg is None or cfg.max_retries <= 0:
+        return RetrySpec(max_retries=0)
+    initial = cfg.initial_backoff_sec if cfg.initial_backoff_sec > 0 else 1
+    mult = cfg.multiplier if cfg.multiplier > 1 else 2.0
+    spec = RetrySpec(
+        max_retries=int(cfg.max_retries),
+        backoff_ticks=_ceil_ticks(initial, tick_seconds),
+        multiplier_q8=int(round(mult * 256)),
+        cap_ticks=_ceil_ticks(cfg.max_backoff_sec, tick_seconds)
+        if cfg.max_backoff_sec > 0 else 0)
+    if not (spec.max_retries <= 32767 and 1 <= spec.backoff_ticks <= 1 << 20
+            and 256 <= spec.multiplier_q8 <= 65535 and 0 <= spec.cap_ticks <= 1 << 20):
+        return None
+    for k in range(1, spec.max_retries + 1):
+        try:
+            host = _ceil_ticks(compute_backoff(step, StepRun(step_id=step.id, attempts=k)),
+                               tick_seconds)
+        except OverflowError:       # the host's own float power gave up
+            return None
+        if wf_backoff_ref(k, spec.backoff_ticks, spec.cap_ticks,
+                          spec.multiplier_q8) != host:
+            return None
+    return spec
+
+
 def dag_from_workflow(workflow: Any, items_len: int,
                       tick_seconds: float = 1.0,
-                      approval_ttl_sec: float = 0.0) -> Optional[DagSpec]:
+                      approval_ttl_sec: float = 0.0,
+                      step_policy: bool = False,
+                      timeout_cutoff: int = 8) -> Optional[DagSpec]:
     """Lower a workflow (a `Workflow`, or its `{"steps": {id: step}}` dict
     form) to a device `DagSpec`; steps are indexed in `workflow.steps` order.
     Returns None when the workflow cannot run on the device, and the caller
     stays on the host engine: more than 64 steps, a step type other than
     worker / approval / delay, a `condition` expression, `delay_until`,
-    `on_error`, a per-step `retry` block, a dependency on a later or unknown
-    step, or a `for_each` over no items (the device cannot complete a step
-    with nothing to emit). `approval_ttl_sec` > 0 gives every approval step
-    that expiry, rounded up to ticks (it needs a pipeline with
-    approvals="external"); 0 lowers approvals without one."""
+    `on_error`, a dependency on a later or unknown step, or a `for_each` over
+    no items (the device cannot complete a step with nothing to emit).
+    `approval_ttl_sec` > 0 gives every approval step that expiry, rounded up
+    to ticks (it needs a pipeline with approvals="external"); 0 lowers
+    approvals without one.
+
+    Without `step_policy` a per-step `retry` block also returns None, steps
+    carry no policy (the pipeline's one `max_retries` applies to all of them,
+    which retries steps the host engine would fail at once) and `timeout_sec`
+    is not lowered. With `step_policy` (a pipeline with step_policy=True)
+    every worker step gets the host's meaning: its `retry` block as a
+    `RetrySpec` (see `lower_retry`; no block is max_retries=0, and a block
+    whose schedule the device cannot reproduce tick for tick returns None),
+    and `timeout_sec` > 0 as `timeout_ticks`, rounded up to ticks and raised
+    to `timeout_cutoff`, the pipeline's floor. On the device a step's timeout
+    is how long results that never came are waited for before the retry; the
+    host engine hands it to the job as its deadline. `retry` and `timeout_sec`
+    on approval and delay steps mean nothing to either engine."""
     steps = _steps_of(workflow)
     ttl = max(0, int(math.ceil(approval_ttl_sec / tick_seconds)))
     if len(steps) > 64:
@@ -163,7 +222,9 @@ def dag_from_workflow(workflow: Any, items_len: int,
         return None
     specs: List[StepSpec] = []
     for i, st in enumerate(steps):
-        if st.condition or st.delay_until or st.on_error or st.retry is not None:
+        if st.condition or st.delay_until or st.on_error:
+            return None
+        if st.retry is not None and not step_policy:
             return None
         deps = []
         for dep in st.depends_on:
@@ -172,13 +233,25 @@ def dag_from_workflow(workflow: Any, items_len: int,
                 return None
             deps.append(j)
         if st.type == "worker":
+            policy = {}
+            if step_policy:
+                retry = lower_retry(st, tick_seconds)
+                if retry is None:
+                    return None
+                timeout = 0
+                if st.timeout_sec > 0:
+                    timeout = max(int(timeout_cutoff),
+                                  _ceil_ticks(st.timeout_sec, tick_seconds))
+                    if timeout > 1 << 30:
+                        return None
+                policy = {"retry": retry, "timeout_ticks": timeout}
             if st.for_each:
                 if items_len <= 0:
                     return None
                 specs.append(StepSpec(WFK_FOR_EACH, deps=deps, fanout=int(items_len),
-                                      max_parallel=int(st.max_parallel)))
+                                      max_parallel=int(st.max_parallel), **policy))
             else:
-                specs.append(StepSpec(WFK_WORKER, deps=deps))
+                specs.append(StepSpec(WFK_WORKER, deps=deps, **policy))
         elif st.type == "approval":
             specs.append(StepSpec(WFK_APPROVAL, deps=deps, ttl_ticks=ttl))
         elif st.type == "delay":
@@ -243,8 +316,13 @@ class DeviceRunTable:
                  approval_ttl_sec: float = 0.0) -> Optional[int]:
         """Lower `workflow` and add it as a template; returns the template id
         to submit() runs of it with, or None if the workflow must stay on the
-        host engine. Events of such runs carry the workflow's step ids."""
-        dag = dag_from_workflow(workflow, items_len, tick_seconds, approval_ttl_sec)
+        host engine. Events of such runs carry the workflow's step ids. On a
+        pipeline with step_policy the steps' `retry` blocks and `timeout_sec`
+        are lowered too (see `dag_from_workflow`)."""
+        dag = dag_from_workflow(
+            workflow, items_len, tick_seconds, approval_ttl_sec,
+            step_policy=bool(getattr(self.pipe, "step_policy", False)),
+            timeout_cutoff=int(getattr(self.pipe, "timeout_cutoff", 8)))
         if dag is None:
             return None
         t = self.pipe.add_template(dag)

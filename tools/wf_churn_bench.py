@@ -35,9 +35,22 @@ scan and the journal pass alone, alternating, on tables of --runs rows and of
 --pass-rows rows (quiet: nothing to report; held: one continuing hold / one
 changed step in every row).
 
+With --step-policy a further mode joins the alternation: the same churn as the
+dynamic window on a pipeline with step_policy=True and no annotated step, so
+every step runs on the default policy and the two windows compute the same
+thing, one through wf_settle, the other through wf_timeout_scan + wf_commit.
+It reports runs/s and the ratio, and times the settle pass and the pair alone,
+alternating on the same tables, at --runs and --pass-rows rows (quiet: no
+DISPATCHED step; busy: one DISPATCHED step with a child in flight in every
+row, which neither changes). --skip-readmit leaves the static baseline out, so
+that a kernel trace of the run holds the pair's kernels from the dynamic
+window only; --settle-pass ROWS runs nothing but the quiet pass timings at
+that size, for a kernel trace of one table size.
+
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --events
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --approvals
+    python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --step-policy
 """
 import argparse
 import json
@@ -72,6 +85,13 @@ def main() -> int:
     ap.add_argument("--pass-rows", type=int, default=1 << 20,
                     help="second table size for the scan / journal pass timings "
                          "(0: no pass timings, for a kernel trace of the churn alone)")
+    ap.add_argument("--step-policy", action="store_true",
+                    help="also run the churn with step_policy=True and default "
+                         "policies (wf_settle in place of the scan / commit pair)")
+    ap.add_argument("--skip-readmit", action="store_true",
+                    help="leave the static readmit baseline out (kernel traces)")
+    ap.add_argument("--settle-pass", type=int, default=0, metavar="ROWS",
+                    help="only time the quiet settle pass and the pair at ROWS rows")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="rehearse the host logic on the reference backend (no timings)")
     args = ap.parse_args()
@@ -118,6 +138,64 @@ def main() -> int:
             self.pairs = []
             return ms
 
+    def settle_pass_times(ext, NR, busy, reps=15):
+        """The settle pass and the pair it replaces (timeout scan + commit)
+        alone on one all-LIVE table of NR rows at stock policies, alternating,
+        one device-event pair per side and round; µs, median (min..max).
+        Quiet: no step is DISPATCHED. Busy: every row has one DISPATCHED step
+        with a child in flight and nothing left to emit, which both sides
+        read and leave as it is, so every round sees the same table."""
+        d = device
+        st = torch.full((NR * 64,), WFS_SUCCEEDED, dtype=torch.uint8, device=d)
+
+        def zi():
+            return torch.zeros(NR * 64, dtype=torch.int32, device=d)
+
+        att, todo, out, done, fail, maxp, nready, dtick = (zi() for _ in range(8))
+        tickb = torch.tensor([5], dtype=torch.int32, device=d)
+        if busy:
+            st.view(NR, 64)[:, 1] = 1              # WFS_DISPATCHED
+            out.view(NR, 64)[:, 1] = 1
+            dtick.view(NR, 64)[:, 1] = 5
+        life = torch.ones(NR, dtype=torch.uint8, device=d)
+        rtmpl = torch.zeros(NR, dtype=torch.int32, device=d)
+        policy = torch.tensor([2, 2, 16, 512], dtype=torch.int32).repeat(64).to(d)
+        timeout = torch.full((64,), 8, dtype=torch.int32, device=d)
+        tcount = torch.zeros(1, dtype=torch.int64, device=d)
+        rcount = torch.zeros(1, dtype=torch.int64, device=d)
+
+        def pair():
+            ext.wf_timeout_scan(st, out, fail, dtick, tickb, 8, tcount)
+            ext.wf_commit(st, att, todo, out, done, fail, maxp, nready, tickb, 2, rcount)
+
+        def settle():
+            ext.wf_settle(st, att, todo, out, fail, maxp, nready, dtick, life, rtmpl,
+                          policy, timeout, tickb, tcount, rcount)
+
+        pair_t, settle_t = Timer(), Timer()
+        for i in range(reps + 3):
+            pair_t(pair)
+            settle_t(settle)
+            sync()
+            if i < 3:                              # warm-up launches
+                pair_t.take_ms(), settle_t.take_ms()
+        assert int(tcount.cpu()[0]) == 0 and int(rcount.cpu()[0]) == 0
+        if not use_gpu:
+            return None
+        return {"rows": NR, "case": "busy" if busy else "quiet",
+                "pair_us": spread([1000 * x for x in pair_t.take_ms()]),
+                "settle_us": spread([1000 * x for x in settle_t.take_ms()])}
+
+    if args.settle_pass:
+        from cordum_amd.ops import get_ext
+        from cordum_amd.ops.pipeline import _RefOps
+
+        ext = get_ext(required=True) if use_gpu else _RefOps()
+        print(json.dumps({"metric": "settle pass vs timeout scan + commit, alone",
+                          "unit": "us", "timed": bool(use_gpu),
+                          "pass_times": [settle_pass_times(ext, args.settle_pass, False)]}))
+        return 0
+
     # ---- dynamic mode ------------------------------------------------------
     dyn = WorkflowPipeline(dags=[dag], dynamic_capacity=args.runs, **common)
     t_admit, t_drain = Timer(), Timer()
@@ -141,6 +219,32 @@ def main() -> int:
                 live[0] += sum(1 for s in got if s >= 0)
         sync()
         return ok, time.perf_counter() - t0
+
+    # ---- dynamic mode with per-step policies (all of them the default) -----
+    sp_window = None
+    if args.step_policy:
+        spp = WorkflowPipeline(dags=[dag], dynamic_capacity=args.runs,
+                               step_policy=True, **common)
+        sp_live = [0]
+        got, _ = spp.admit([0] * args.runs)
+        sp_live[0] = sum(1 for s in got if s >= 0)
+        assert sp_live[0] == args.runs
+
+        def sp_window(n_ticks):
+            ok = 0
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(n_ticks):
+                spp.tick()
+                _, _, states = spp.drain_completed()
+                ok += sum(1 for s in states if s == WFS_SUCCEEDED)
+                sp_live[0] -= len(states)
+                want = args.runs - sp_live[0]
+                if want:
+                    got, _ = spp.admit([0] * want)
+                    sp_live[0] += sum(1 for s in got if s >= 0)
+            sync()
+            return ok, time.perf_counter() - t0
 
     # ---- dynamic mode with the step journal, through DeviceRunTable --------
     ev_window = None
@@ -269,6 +373,10 @@ def main() -> int:
         return ok1 - ok0, time.perf_counter() - t0
 
     modes = [("dynamic", dyn_window), ("readmit", sta_window)]
+    if args.skip_readmit:
+        modes.pop()
+    if sp_window is not None:
+        modes.insert(1, ("step_policy", sp_window))
     if ev_window is not None:
         modes.insert(1, ("events", ev_window))
     if ap_window is not None:
@@ -316,14 +424,29 @@ def main() -> int:
         "runs": args.runs, "fanout": args.fanout, "workers": args.workers,
         "ticks_per_window": args.ticks, "repeats": args.repeats,
         "dynamic_runs_per_s": spread(rate["dynamic"]),
-        "readmit_runs_per_s": spread(rate["readmit"]),
-        "dynamic_over_readmit": round(
-            statistics.median(rate["dynamic"]) / max(1e-9, statistics.median(rate["readmit"])), 3),
         "ms_per_tick": {k: spread(v) for k, v in tick_ms.items()},
         "ms_per_call_device_events": {k: spread(v) for k, v in call_ms.items() if v},
         "graph": {"dynamic": bool(dyn._wf_graph), "readmit": bool(sta._wf_graph)},
         "live_at_end": live[0],
     }
+    if not args.skip_readmit:
+        out["readmit_runs_per_s"] = spread(rate["readmit"])
+        out["dynamic_over_readmit"] = round(
+            statistics.median(rate["dynamic"]) / max(1e-9, statistics.median(rate["readmit"])), 3)
+    if sp_window is not None:
+        out["step_policy"] = {
+            "runs_per_s": spread(rate["step_policy"]),
+            "step_policy_over_dynamic": round(
+                statistics.median(rate["step_policy"])
+                / max(1e-9, statistics.median(rate["dynamic"])), 3),
+            # per repeat, the two windows back to back
+            "ratio_per_repeat": [round(a / max(1e-9, b), 3) for a, b in
+                                 zip(rate["step_policy"], rate["dynamic"])],
+            "graph": bool(spp._wf_graph),
+            "pass_times": [settle_pass_times(dyn.ext, n, busy) for n in
+                           ((args.runs, args.pass_rows) if use_gpu else (64,))
+                           for busy in (False, True)] if args.pass_rows else [],
+        }
     if ev_window is not None:
         per_tick = statistics.median(ev_rate) * statistics.median(tick_ms["events"]) / 1000.0
         # one pass: a life byte per slot; generation + shadow generation,
