@@ -2144,6 +2144,49 @@ __global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_bits_kernel(
                                tile_dims, out_first, J, R, tiles_per_chunk);
 }
 
+// K1 from compact rows: cols[J][L] holds one word per LIVE dimension (a
+// dimension some rule constrains, ops/policy_mfma.py live_dims), so the
+// staged batch carries L words per job instead of nine. col_map is the
+// d -> column map, 4 bits per dimension, 0xF = no column: passed by value, so
+// it is wave-uniform and part of the captured launch like R. A dimension
+// without a column gets a zero fragment; the rule scan never looks at it
+// (tile_dims has its bit clear in every tile, the binding checks that).
+// With L == 0 nothing is read from cols. Only the word's source differs from
+// the bits kernel; the expansion and the scan are the same.
+template <int TJ>
+__global__ __launch_bounds__(BLOCK) void policy_first_match_mfma_cols_kernel(
+    const long long* __restrict__ cols,       // [J,L] (1-word vocab)
+    int L, unsigned long long col_map,
+    const signed char* __restrict__ b_pack,
+    const int* __restrict__ cards,
+    const signed char* __restrict__ rule_secrets,
+    const unsigned char* __restrict__ job_secrets,
+    const int* __restrict__ tile_dims,
+    int* __restrict__ out_first,
+    int J, int R, int tiles_per_chunk)
+{
+    const int lane = threadIdx.x % WAVE;
+    const int shift = (lane >> 4) * 16;
+    v4i afrag[TJ][9];
+    #pragma unroll
+    for (int t = 0; t < TJ; ++t) {
+        const int job = (blockIdx.x * TJ + t) * 16 + (lane & 15);
+        #pragma unroll
+        for (int d = 0; d < 9; ++d) {
+            const int c = (int)((col_map >> (4 * d)) & 0xFull);
+            unsigned long long w = 0;
+            if (c < L && job < J)
+                w = (unsigned long long)cols[(size_t)job * L + c];
+            const unsigned int slice = (unsigned int)(w >> shift) & 0xFFFFu;
+            #pragma unroll
+            for (int q = 0; q < 4; ++q)
+                afrag[t][d][q] = (int)((((slice >> (4 * q)) & 0xFu) * 0x00204081u) & 0x01010101u);
+        }
+    }
+    mfma_first_match_tiles<TJ>(afrag, b_pack, cards, rule_secrets, job_secrets,
+                               tile_dims, out_first, J, R, tiles_per_chunk);
+}
+
 // ---------------------------------------------------------------------------
 // Tick-fusion kernels: device-side compaction + count-pointer variants so a
 // whole single-GPU control-plane tick is a fixed kernel sequence (no host
@@ -3204,6 +3247,72 @@ void policy_first_match_mfma_bits_into(
     else launch(policy_first_match_mfma_bits_kernel<1>);
 }
 
+// K1 from compact rows (policy_first_match_mfma_cols_kernel). The checks of
+// the bits variant, plus the ones that keep a stale column map loud: the map
+// must name exactly the columns 0..L-1, ascending in d, and every dimension
+// some rule tile scans must have a column. tile_dims lives on the device, so
+// that last check reads it back: not possible (and not needed) while the
+// stream is being captured, where the call repeats an eager warm-up call
+// with the same arguments that was checked.
+void policy_first_match_mfma_cols_into(
+    torch::Tensor cols, int64_t col_map,
+    torch::Tensor b_pack, torch::Tensor cards,
+    torch::Tensor rule_secrets, torch::Tensor job_secrets,
+    torch::Tensor tile_dims, int64_t n_rules, torch::Tensor out, int64_t job_tiles)
+{
+    CHECK_DEV(cols); CHECK_DEV(b_pack);
+    CHECK_CONTIG(cols);
+    TORCH_CHECK(job_tiles == 1 || job_tiles == 2, "job_tiles must be 1 or 2");
+    TORCH_CHECK(cols.dim() == 2 && cols.scalar_type() == torch::kInt64 && cols.size(1) <= 9,
+                "compact K1 needs cols [J,L] int64 with L <= 9 (1-word vocab)");
+    const int J = (int)cols.size(0), R = (int)n_rules, L = (int)cols.size(1);
+    TORCH_CHECK(job_secrets.size(0) >= J && out.size(0) >= J, "job tensors must cover J");
+    TORCH_CHECK(col_map >= 0 && (col_map >> 36) == 0, "col_map holds 9 nibbles");
+    unsigned map_dims = 0;
+    int next_col = 0;
+    for (int d = 0; d < 9; ++d) {
+        const int c = (int)((col_map >> (4 * d)) & 0xF);
+        if (c == 0xF) continue;
+        TORCH_CHECK(c == next_col, "col_map must number the live dims 0..L-1 in ascending d");
+        ++next_col;
+        map_dims |= 1u << d;
+    }
+    TORCH_CHECK(next_col == L, "col_map names ", next_col, " columns, cols has ", L);
+    const int TJ = (int)job_tiles;
+    const int Jt = ((J + 15) / 16 + TJ - 1) / TJ;   // blocks of TJ job tiles
+    const int Rt = (R + 15) / 16;
+    if (J == 0 || R == 0) return;
+    TORCH_CHECK(b_pack.size(0) >= Rt && tile_dims.size(0) >= Rt &&
+                rule_secrets.size(0) >= Rt * 16 && cards.size(0) >= Rt * 16,
+                "rule pack smaller than n_rules");
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &capturing) == hipSuccess,
+                "hipStreamIsCapturing failed");
+    if (capturing == hipStreamCaptureStatusNone) {
+        const torch::Tensor td = tile_dims.narrow(0, 0, Rt).cpu();
+        const int* p = td.data_ptr<int>();
+        unsigned scanned = 0;
+        for (int rt = 0; rt < Rt; ++rt) scanned |= (unsigned)p[rt];
+        TORCH_CHECK((scanned & 0x1FFu & ~map_dims) == 0,
+                    "col_map lacks a dimension the packed policy scans (stale map?): "
+                    "tile_dims union ", scanned & 0x1FFu, ", map dims ", map_dims);
+    }
+    int nchunks = std::max(1, std::min((Rt + 3) / 4, std::max(1, 2048 / std::max(Jt, 1))));
+    const int tiles_per_chunk = (Rt + nchunks - 1) / nchunks;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(Jt, nchunks), dim3(BLOCK), 0, cur_stream(),
+            (const long long*)cols.data_ptr<int64_t>(), L, (unsigned long long)col_map,
+            (const signed char*)b_pack.data_ptr<int8_t>(),
+            cards.data_ptr<int>(),
+            (const signed char*)rule_secrets.data_ptr<int8_t>(),
+            job_secrets.data_ptr<uint8_t>(),
+            tile_dims.data_ptr<int>(),
+            out.data_ptr<int>(), J, R, tiles_per_chunk);
+    };
+    if (TJ == 2) launch(policy_first_match_mfma_cols_kernel<2>);
+    else launch(policy_first_match_mfma_cols_kernel<1>);
+}
+
 void gate_route(torch::Tensor first, torch::Tensor decisions, torch::Tensor out_decision,
                 torch::Tensor denied_slots, torch::Tensor denied_count,
                 torch::Tensor allowed_slots, torch::Tensor allowed_count,
@@ -3971,6 +4080,67 @@ void synthetic_fresh_stamped(torch::Tensor any_bits,   // [B,7,W] int64 (host)
     cordum_enc::encode_batch(a, (int)threads, (int)isa_cap);
 }
 
+// synthetic_fresh_stamped into compact rows: cols [B,L] holds one word per
+// dimension the compiled policy reads (ops/policy_mfma.py), col_of_* is the
+// column of each synthetic dim or -1 where the policy does not read it. Same
+// draws, same stamp; a dim without a column is drawn and not stored. Writes
+// nothing else: the other columns and the secrets bytes behind the rows keep
+// what the caller put there (zeros, set once at allocation).
+void synthetic_fresh_compact(torch::Tensor cols,        // [B,L] int64 (host)
+                             torch::Tensor tenant_lut, torch::Tensor topic_lut,
+                             torch::Tensor risk_lut, torch::Tensor req_lut,
+                             int64_t seed, int64_t step,
+                             int64_t col_of_tenant, int64_t col_of_topic,
+                             int64_t col_of_risk, int64_t col_of_requires,
+                             c10::optional<torch::Tensor> payload,  // [B*words] int32 (host)
+                             int64_t payload_words,
+                             int64_t threads, int64_t isa_cap)
+{
+    TORCH_CHECK(!cols.is_cuda(), "synthetic_fresh_compact is a host encoder");
+    CHECK_CONTIG(cols);
+    CHECK_CONTIG(tenant_lut); CHECK_CONTIG(topic_lut);
+    CHECK_CONTIG(risk_lut); CHECK_CONTIG(req_lut);
+    TORCH_CHECK(cols.dim() == 2 && cols.scalar_type() == torch::kInt64,
+                "cols must be [B,L] int64");
+    cordum_enc::EncodeJob a;
+    a.B = cols.size(0);
+    a.W = 1;
+    a.V = tenant_lut.size(0);
+    const int64_t L = cols.size(1);
+    for (const torch::Tensor* l : {&tenant_lut, &topic_lut, &risk_lut, &req_lut})
+        TORCH_CHECK(l->dim() == 2 && l->size(0) == a.V && l->size(1) == 1,
+                    "compact rows need 1-word LUTs [V,1]");
+    const int64_t c4[4] = {col_of_tenant, col_of_topic, col_of_risk, col_of_requires};
+    for (int i = 0; i < 4; ++i) {
+        TORCH_CHECK(c4[i] >= -1 && c4[i] < L, "column index out of range");
+        for (int k = 0; k < i; ++k)
+            TORCH_CHECK(c4[i] < 0 || c4[i] != c4[k], "two dims share a column");
+    }
+    // both row pointers are the one array; with L == 0 every column is -1
+    // and it is never dereferenced
+    a.any = a.all = cols.data_ptr<int64_t>();
+    a.any_stride = a.all_stride = L;
+    a.tenant_lut = tenant_lut.data_ptr<int64_t>();
+    a.topic_lut = topic_lut.data_ptr<int64_t>();
+    a.risk_lut = risk_lut.data_ptr<int64_t>();
+    a.req_lut = req_lut.data_ptr<int64_t>();
+    a.seed = (uint64_t)seed;
+    a.step = (uint64_t)step;
+    a.dim_tenant = (int)col_of_tenant;
+    a.dim_topic = (int)col_of_topic;
+    a.dim_risk = (int)col_of_risk;
+    a.all_requires = (int)col_of_requires;
+    a.payload = nullptr;
+    a.payload_words = payload_words;
+    if (payload.has_value()) {
+        TORCH_CHECK(!payload->is_cuda() && payload->is_contiguous() &&
+                    payload->scalar_type() == torch::kInt32 && payload_words > 0 &&
+                    payload->numel() >= a.B * payload_words, "bad payload ring buffer");
+        a.payload = payload->data_ptr<int32_t>();
+    }
+    cordum_enc::encode_batch(a, (int)threads, (int)isa_cap);
+}
+
 void pack_jobs_mfma_dev(torch::Tensor any_bits, torch::Tensor all_bits,
                         torch::Tensor a_pack)
 {
@@ -4026,6 +4196,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("seed"), py::arg("step"), py::arg("dim_tenant"), py::arg("dim_topic"),
           py::arg("dim_risk"), py::arg("all_requires"), py::arg("payload"),
           py::arg("payload_words"), py::arg("threads") = 1, py::arg("isa_cap") = -1);
+    m.def("synthetic_fresh_compact", &synthetic_fresh_compact,
+          py::call_guard<py::gil_scoped_release>(),
+          "synthetic_fresh_stamped into compact rows: one column per dim the policy reads",
+          py::arg("cols"), py::arg("tenant_lut"), py::arg("topic_lut"),
+          py::arg("risk_lut"), py::arg("req_lut"), py::arg("seed"), py::arg("step"),
+          py::arg("col_of_tenant"), py::arg("col_of_topic"), py::arg("col_of_risk"),
+          py::arg("col_of_requires"), py::arg("payload"), py::arg("payload_words"),
+          py::arg("threads") = 1, py::arg("isa_cap") = -1);
     m.def("encoder_isa_level", [] { return cordum_enc::max_isa_level(); },
           "widest encoder ISA this CPU runs (0 baseline, 1 AVX2, 2 AVX-512DQ)");
     m.def("tick_prologue", &tick_prologue,
@@ -4033,6 +4211,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("policy_first_match_mfma_bits_into", &policy_first_match_mfma_bits_into,
           "fused tick 3/5: K1 MFMA with A fragments built from the staged bit words",
           py::arg("any_bits"), py::arg("all_bits"), py::arg("b_pack"), py::arg("cards"),
+          py::arg("rule_secrets"), py::arg("job_secrets"), py::arg("tile_dims"),
+          py::arg("n_rules"), py::arg("out"), py::arg("job_tiles") = 1);
+    m.def("policy_first_match_mfma_cols_into", &policy_first_match_mfma_cols_into,
+          "fused tick 3/5, compact staging: K1 MFMA with A fragments built from the "
+          "live-dimension columns",
+          py::arg("cols"), py::arg("col_map"), py::arg("b_pack"), py::arg("cards"),
           py::arg("rule_secrets"), py::arg("job_secrets"), py::arg("tile_dims"),
           py::arg("n_rules"), py::arg("out"), py::arg("job_tiles") = 1);
     m.def("gate_route", &gate_route,

@@ -1,8 +1,8 @@
 // Host-side synthetic job-batch encoder for the end-to-end ingest window.
 //
 // Plain C++17, no torch / HIP dependency: the extension wrapper
-// (cordum_kernels.hip) and the stand-alone sanitizer program
-// (tests/native/encode_check.cpp) both include this file.
+// (cordum_kernels.hip) and the stand-alone sanitizer programs
+// (tests/native/encode_check.cpp, encode_compact_check.cpp) include this file.
 //
 // Draws are those of synthetic_fresh, bit for bit: per job i,
 //   h0 = splitmix64(base ^ i), h1 = splitmix64(h0), h2 = splitmix64(h1)
@@ -11,6 +11,14 @@
 // the four 32-bit halves of h0/h1, the risk / requires coin flips compare the
 // halves of h2 against fixed cut-offs. Only the four synthetic dims of a row
 // are written; the other dims are left as they are.
+//
+// One loop serves two destination layouts. Full: `any` is [B,7,W], `all` is
+// [B,2,W] and dim_* / all_requires index the dim inside a row (the default:
+// strides 0). Compact: both base pointers are the same [B,L] array of the
+// columns the compiled policy reads, both strides are L, and dim_* /
+// all_requires are column numbers; a negative one means the policy does not
+// read that dim, and its store is skipped (the draws are made all the same,
+// so every other value is what the full layout gets).
 //
 // What is different from the serial loop is the schedule, not the values:
 // jobs are hashed a block at a time into small arrays (a loop the compiler
@@ -32,17 +40,23 @@
 namespace cordum_enc {
 
 struct EncodeJob {
-    int64_t* any;            // [B,7,W]
-    int64_t* all;            // [B,2,W]
+    int64_t* any;            // [B,7,W], or rows of any_stride*W words
+    int64_t* all;            // [B,2,W], or rows of all_stride*W words
     const int64_t* tenant_lut;  // [V,W]
     const int64_t* topic_lut;
     const int64_t* risk_lut;
     const int64_t* req_lut;
     int64_t B, W, V;
     uint64_t seed, step;
+    // destination offset of each synthetic dim inside its row, in units of W
+    // words (tenant/topic/risk from `any`, requires from `all`); < 0: skip
     int dim_tenant, dim_topic, dim_risk, all_requires;
     int32_t* payload;        // [B,payload_words] or nullptr: no stamp
     int64_t payload_words;
+    // row strides of `any` / `all` in units of W words; 0: the full layout's
+    // 7 and 2, so a value-initialised EncodeJob writes [B,7,W] / [B,2,W]
+    int64_t any_stride = 0;
+    int64_t all_stride = 0;
 };
 
 constexpr int kBlock = 64;
@@ -68,6 +82,10 @@ __attribute__((always_inline)) static inline void encode_range_impl(
     const uint64_t base = batch_base(a.seed, a.step);
     const uint64_t v = (uint64_t)a.V;
     const int64_t W = a.W;
+    const int64_t sa = a.any_stride > 0 ? a.any_stride : 7;
+    const int64_t sl = a.all_stride > 0 ? a.all_stride : 2;
+    const bool st = a.dim_tenant >= 0, so = a.dim_topic >= 0;
+    const bool sr = a.dim_risk >= 0, sq = a.all_requires >= 0;
     const int32_t stamp = (int32_t)(uint32_t)a.step;
     uint32_t t_idx[kBlock], o_idx[kBlock], r_idx[kBlock], q_idx[kBlock];
     uint32_t c_risk[kBlock], c_req[kBlock];
@@ -86,20 +104,22 @@ __attribute__((always_inline)) static inline void encode_range_impl(
             c_risk[k] = (uint32_t)h2;
             c_req[k] = (uint32_t)(h2 >> 32);
         }
-        // phase 2: gathers + row stores
-        if (W == 1) {
-            int64_t* arow = a.any + (size_t)b0 * 7;
-            int64_t* lrow = a.all + (size_t)b0 * 2;
-            for (int k = 0; k < n; ++k, arow += 7, lrow += 2) {
-                arow[a.dim_tenant] = a.tenant_lut[t_idx[k]];
-                arow[a.dim_topic] = a.topic_lut[o_idx[k]];
-                arow[a.dim_risk] = c_risk[k] < kRiskCut ? a.risk_lut[r_idx[k]] : 0;
-                lrow[a.all_requires] = c_req[k] < kReqCut ? a.req_lut[q_idx[k]] : 0;
+        // phase 2: gathers + row stores (none where no dim has a
+        // destination: the row pointers may then be null)
+        if (!(st || so || sr || sq)) {
+        } else if (W == 1) {
+            int64_t* arow = a.any + (size_t)b0 * sa;
+            int64_t* lrow = a.all + (size_t)b0 * sl;
+            for (int k = 0; k < n; ++k, arow += sa, lrow += sl) {
+                if (st) arow[a.dim_tenant] = a.tenant_lut[t_idx[k]];
+                if (so) arow[a.dim_topic] = a.topic_lut[o_idx[k]];
+                if (sr) arow[a.dim_risk] = c_risk[k] < kRiskCut ? a.risk_lut[r_idx[k]] : 0;
+                if (sq) lrow[a.all_requires] = c_req[k] < kReqCut ? a.req_lut[q_idx[k]] : 0;
             }
         } else {
             for (int k = 0; k < n; ++k) {
-                int64_t* arow = a.any + (size_t)(b0 + k) * 7 * W;
-                int64_t* lrow = a.all + (size_t)(b0 + k) * 2 * W;
+                int64_t* arow = a.any + (size_t)(b0 + k) * sa * W;
+                int64_t* lrow = a.all + (size_t)(b0 + k) * sl * W;
                 const bool has_risk = c_risk[k] < kRiskCut;
                 const bool has_req = c_req[k] < kReqCut;
                 const int64_t* tl = a.tenant_lut + (size_t)t_idx[k] * W;
@@ -107,10 +127,10 @@ __attribute__((always_inline)) static inline void encode_range_impl(
                 const int64_t* rl = a.risk_lut + (size_t)r_idx[k] * W;
                 const int64_t* ql = a.req_lut + (size_t)q_idx[k] * W;
                 for (int64_t w = 0; w < W; ++w) {
-                    arow[a.dim_tenant * W + w] = tl[w];
-                    arow[a.dim_topic * W + w] = ol[w];
-                    arow[a.dim_risk * W + w] = has_risk ? rl[w] : 0;
-                    lrow[a.all_requires * W + w] = has_req ? ql[w] : 0;
+                    if (st) arow[a.dim_tenant * W + w] = tl[w];
+                    if (so) arow[a.dim_topic * W + w] = ol[w];
+                    if (sr) arow[a.dim_risk * W + w] = has_risk ? rl[w] : 0;
+                    if (sq) lrow[a.all_requires * W + w] = has_req ? ql[w] : 0;
                 }
             }
         }

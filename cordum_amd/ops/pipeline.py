@@ -215,6 +215,35 @@ class SyntheticEncoder:
                                     self.encode_threads if threads is None else threads,
                                     isa_cap)
 
+    def compact_columns(self, live) -> tuple:
+        """Columns of the four synthetic dims (tenant, topic, risk, requires)
+        in a compact row over the live dimensions `live` (ascending, 0..8:
+        the 7 any-of then the 2 all-of); -1 where the policy does not read
+        the dim."""
+        from .policy_mfma import col_of
+
+        DIM_TENANT, DIM_TOPIC, DIM_RISK, ALL_REQUIRES = self._dims
+        return (col_of(live, DIM_TENANT), col_of(live, DIM_TOPIC),
+                col_of(live, DIM_RISK), col_of(live, 7 + ALL_REQUIRES))
+
+    def fresh_compact(self, cols: torch.Tensor, step: int, ext, columns,
+                      payload: torch.Tensor, payload_words: int,
+                      threads: Optional[int] = None, isa_cap: int = -1) -> None:
+        """fresh_stamped into compact rows (ext.synthetic_fresh_compact):
+        cols is [B, L] int64, `columns` what compact_columns returned for the
+        same live set. The draws and the payload stamp are those of
+        fresh_stamped for the same (seed, step); a dim with column -1 is not
+        stored. Like fresh_fast it writes nothing else: the other columns
+        and the secrets bytes keep the zeros they were allocated with."""
+        assert self.W == 1, "compact rows need the 1-word vocab"
+        ct, co, cr, cq = columns
+        ext.synthetic_fresh_compact(cols, self.tenant_lut, self.topic_lut,
+                                    self.risk_lut, self.req_lut,
+                                    self.seed, step, ct, co, cr, cq,
+                                    payload, payload_words,
+                                    self.encode_threads if threads is None else threads,
+                                    isa_cap)
+
 
 class _RefOps:
     """CPU backend with the HIP extension's call signatures, built on the
@@ -567,6 +596,26 @@ def alloc_batch_staging(B: int, W: int, device=None, pin: bool = False):
     return JobBatch(any_b, all_b, sec, mcp_b, used), buf
 
 
+def alloc_compact_staging(B: int, L: int, device=None, pin: bool = False):
+    """The compact twin of alloc_batch_staging for the MFMA K1: only what
+    that kernel can be affected by. cols int64[B, L] (one word per LIVE set
+    dimension of the compiled policy, ascending; policy_mfma.live_dims) at
+    offset 0, then secrets uint8[B] at offset 8*B*L, the whole padded to a
+    multiple of 8 bytes. Same layout on the host (pinned) and device sides,
+    so one copy_ stages it. L == 0 (a bundle of catch-all rules) leaves an
+    empty cols view and the secrets alone.
+    Returns (cols, secrets, flat uint8 buffer)."""
+    assert B >= 1 and 0 <= L <= 9
+    nbytes = ((B * L * 8 + B + 7) // 8) * 8
+    if pin:
+        buf = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+    else:
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    cols = buf[0:B * L * 8].view(torch.int64).view(B, L)
+    sec = buf[B * L * 8:B * L * 8 + B]
+    return cols, sec, buf
+
+
 def alloc_result_block(B: int, device=None, pin: bool = False):
     """Per-tick results as views of ONE contiguous buffer (the egress twin of
     alloc_batch_staging): checksums int32[B] | counters int32[4] | decisions
@@ -603,7 +652,26 @@ class DevicePipeline:
         pad_cap: Optional[int] = None,
         unfused_tick: bool = False,
         k1_job_tiles: int = 2,
+        compact_staging: Optional[bool] = None,
     ):
+        """compact_staging: e2e_run stages, per step, only the descriptor
+        words the compiled policy reads (one int64 column per live set
+        dimension + the secrets byte, alloc_compact_staging) instead of the
+        full JobBatch layout, and replays a second set of captured graphs
+        whose K1 reads those columns. None turns it on exactly where the
+        fused MFMA-from-bits tick with mfma_pack_on_device is active (single
+        rank, 1-word vocabulary, CUDA, ext backend); False keeps the
+        full-layout staging. tick(), tick_async(), tick_e2e() and every
+        other path read the full-layout tensors through the first set of
+        graphs either way.
+
+        The live map, the compact buffers and the compact graphs all hang on
+        mfma_policy, which this class packs in __init__ only (a pipeline
+        serves one compiled policy). _build_compact() derives all three from
+        it; a path that packs mfma_policy again has to call it again, and
+        the K1 binding refuses a map that lacks a dimension the packed
+        policy scans, so forgetting that is an error and not a wrong
+        decision."""
         # 16-job tiles each K1 wave holds in registers (1 or 2), so one
         # B-fragment load and one cards gather serve that many MFMAs.
         # Measured at the bench shape (kernel trace, 4 x 300 ticks each,
@@ -781,9 +849,44 @@ class DevicePipeline:
                 a_pack, _ = pack_jobs_mfma(jb_host)
                 self.mfma_a_packs.append(a_pack.to(device))
         self._fused_capable = device.type == "cuda" and self.world == 1 and backend != "ref"
+        compact_ok = (self._fused_capable and self._use_mfma
+                      and self._mfma_device_pack and not self._unfused_tick)
+        if compact_staging and not compact_ok:
+            raise ValueError("compact_staging needs the fused MFMA-from-bits tick "
+                             "(single rank, 1-word vocabulary, CUDA, ext backend, "
+                             "mfma_pack_on_device)")
+        self._compact = compact_ok if compact_staging is None else bool(compact_staging)
+        if self._compact:
+            self._build_compact()
         self._tick = 0
         self.total_completed = 0
         self.total_denied = 0
+
+    def _build_compact(self) -> None:
+        """Everything the compact staging path derives from mfma_policy: the
+        live dimensions and their packed column map, the per-slot device
+        buffers (filled from the pre-staged full-layout batches, so they
+        never hold garbage) and an empty set of compact graphs. Also drops
+        the host side of an earlier build: e2e_run allocates it again."""
+        from .policy_mfma import col_map, gather_live_cols, live_dims
+
+        self._live = live_dims(self.mfma_policy)
+        self._col_map = col_map(self._live)
+        self.compact_cols: List[torch.Tensor] = []
+        self.compact_secrets: List[torch.Tensor] = []
+        self.compact_bufs: List[torch.Tensor] = []
+        for jb in self.batches:
+            cols, sec, buf = alloc_compact_staging(self.B, len(self._live),
+                                                   device=self.device)
+            cols.copy_(gather_live_cols(jb, self._live))
+            sec.copy_(jb.secrets)
+            self.compact_cols.append(cols)
+            self.compact_secrets.append(sec)
+            self.compact_bufs.append(buf)
+        self._cgraphs = {}
+        for name in ("_e2e_ccols", "_e2e_cbufs", "_e2e_ccolumns"):
+            if hasattr(self, name):
+                delattr(self, name)
 
 
     def _spread(self, pick):
@@ -808,7 +911,7 @@ class DevicePipeline:
         self.valid_buf.copy_(valid.sum().to(torch.int32).reshape(1))
 
     # -- fused single-GPU tick (hipGraph-captured per ring slot) -------------------
-    def _fused_body(self, slot: int) -> None:
+    def _fused_body(self, slot: int, compact: bool = False) -> None:
         """The whole tick as a fixed kernel sequence over ring slot `slot`'s
         tensors — no host decisions, no staging copies; one captured graph
         per ring slot (the boundary/graph-replay costs in
@@ -819,7 +922,12 @@ class DevicePipeline:
         Ten of the older sequence's launches ran 4.4-8.8 us each over a few
         thousand threads of work (profiles/r49_e2e_overlap_ktrace_stats.txt),
         and the main stream's span per step, not the host encode, was what
-        bounded the pipelined ingest step (profiles/r51_ktrace_before.txt)."""
+        bounded the pipelined ingest step (profiles/r51_ktrace_before.txt).
+
+        compact=True is the same tick with K1 reading the slot's compact
+        buffer (live-dimension columns + secrets) instead of the full-layout
+        batch; the other four launches are the same calls."""
+        assert not compact or self._compact, "compact staging is off"
         if self._unfused_tick:
             return self._unfused_body(slot)
         B = self.B
@@ -840,7 +948,14 @@ class DevicePipeline:
                                    self.valid_buf, full_mask, self.pick_buf)
         # 3) K1; the MFMA variant builds its A fragments from the staged bit
         # words in registers (no pack launch, no pack buffer)
-        if self._use_mfma:
+        if compact:
+            ext.policy_first_match_mfma_cols_into(
+                self.compact_cols[slot], self._col_map, self.mfma_policy.b_pack,
+                self.mfma_policy.cards, self.mfma_policy.secrets,
+                self.compact_secrets[slot], self.mfma_policy.tile_dims,
+                self.compiled.n_rules, self.first_buf, self._k1_job_tiles)
+            first = self.first_buf
+        elif self._use_mfma:
             ext.policy_first_match_mfma_bits_into(
                 jb.any_bits, jb.all_bits, self.mfma_policy.b_pack,
                 self.mfma_policy.cards, self.mfma_policy.secrets, jb.secrets,
@@ -972,6 +1087,34 @@ class DevicePipeline:
         self.dlq_head.zero_()
         self.dlq_ring.fill_(-1)
         self.acc_counts.zero_()
+        torch.cuda.synchronize(self.device)
+
+    def _ensure_compact_graphs(self) -> None:
+        """The second set of graphs, one per ring slot, over _fused_body's
+        compact variant; captured on e2e_run's first call the way
+        _ensure_graphs captures the first set (which must exist: its warm-up
+        has primed the kernels and it owns the reset below)."""
+        if self._cgraphs:
+            return
+        self._ensure_graphs()
+        keep = (self.dlq_head.clone(), self.dlq_ring.clone(), self.acc_counts.clone())
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for slot in range(len(self.batches)):
+                self._fused_body(slot, compact=True)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        for slot in range(len(self.batches)):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._fused_body(slot, compact=True)
+            self._cgraphs[slot] = g
+        # the eager warm-up ran the body for real: put the durable DLQ ring
+        # and the stats accumulator back to what the counted ticks left
+        self.dlq_head.copy_(keep[0])
+        self.dlq_ring.copy_(keep[1])
+        self.acc_counts.copy_(keep[2])
         torch.cuda.synchronize(self.device)
 
     def _replay_fused(self) -> None:
@@ -1202,6 +1345,25 @@ class DevicePipeline:
             from concurrent.futures import ThreadPoolExecutor
 
             self._e2e_pool = ThreadPoolExecutor(max_workers=2)
+        compact = self._compact
+        if compact and not hasattr(self, "_e2e_cbufs"):
+            # compact staging: the same ring of nhost pinned host buffers in
+            # the compact layout (live-dimension columns + secrets, zeroed
+            # once here: the encoder writes only the synthetic dims' columns),
+            # mirrored by the device slots' compact buffers, so one copy_
+            # per step stages the descriptors. The reuse-distance argument
+            # above is about buffer indices and event order only and holds
+            # unchanged: 4 host buffers, 2 device slots.
+            trip = [alloc_compact_staging(B, len(self._live), pin=True)
+                    for _ in range(nhost)]
+            self._e2e_ccols = [t[0] for t in trip]
+            self._e2e_cbufs = [t[2] for t in trip]
+            self._e2e_ccolumns = self._e2e_encs[0].compact_columns(self._live)
+        if compact:
+            self._ensure_compact_graphs()
+        graphs = self._cgraphs if compact else self._graphs
+        dev_bufs = self.compact_bufs if compact else self.batch_bufs
+        host_bufs = self._e2e_cbufs if compact else self._e2e_host_bufs
 
         completed = denied = 0
         lats = [0.0] * steps
@@ -1209,8 +1371,17 @@ class DevicePipeline:
 
         def encode(s: int):
             t_enc[s] = time.perf_counter()
+            payload = self._e2e_payloads[s % len(self._e2e_payloads)]
+            if compact:
+                # same per-slot encoder, same (seed, step): the batch is the
+                # one the full-layout path encodes, minus the words K1 cannot
+                # be affected by
+                self._e2e_encs[s % nhost].fresh_compact(
+                    self._e2e_ccols[s % nhost], s, self.ext, self._e2e_ccolumns,
+                    payload, self.payload_words)
+                return
             self._encode_host(s, self._e2e_hosts2[s % nhost], self._e2e_encs[s % nhost],
-                              self._e2e_payloads[s % len(self._e2e_payloads)])
+                              payload)
 
         def harvest(s_prev: int) -> None:
             nonlocal completed, denied
@@ -1249,14 +1420,13 @@ class DevicePipeline:
             # first (the old order) serialized [H2D][graph][D2H] on the
             # device and cost ~40% of the step
             with torch.cuda.stream(self._e2e_copy_stream):
-                self.batch_bufs[slot].copy_(
-                    self._e2e_host_bufs[s % nhost], non_blocking=True)
+                dev_bufs[slot].copy_(host_bufs[s % nhost], non_blocking=True)
                 self.payloads[slot].copy_(
                     self._e2e_payloads[s % len(self._e2e_payloads)],
                     non_blocking=True)
                 self._e2e_in_ev[slot].record(self._e2e_copy_stream)
             torch.cuda.current_stream(self.device).wait_event(self._e2e_in_ev[slot])
-            self._graphs[slot].replay()
+            graphs[slot].replay()
             # checksums + counters + decisions: one block, one D2H
             self._e2e_out_blocks[slot].copy_(self._res_block, non_blocking=True)
             self._e2e_ev[slot].record()

@@ -27,7 +27,7 @@ benchmark policies); MCP-constrained rules use the default bitset kernel.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Tuple
+from typing import List, Sequence, Tuple
 
 import torch
 
@@ -103,11 +103,63 @@ def pack_policy_mfma(c: CompiledPolicy) -> MfmaPolicy:
     secrets = torch.full((Rt * 16,), -1, dtype=torch.int8)
     secrets[:R] = c.secrets
     # per-tile union of constrained dims: a dim with card==0 for every rule
-    # in the tile auto-passes, so the kernel skips its MFMA + B load
-    used = (cards.view(Rt, 16, N_DIMS) != 0).any(dim=1)  # [Rt, 9]
+    # in the tile auto-passes, so the kernel skips its MFMA + B load. Real
+    # rules only: the padding rules' impossible card is a second guard behind
+    # the scan's `rule < R` test, not a constraint a job has to be staged
+    # for, and must not make dim 7 live (live_dims below) in a bundle no rule
+    # of which reads it
+    real = torch.zeros(Rt * 16, N_DIMS, dtype=torch.bool)
+    real[:R] = cards[:R] != 0
+    used = real.view(Rt, 16, N_DIMS).any(dim=1)  # [Rt, 9]
     tile_dims = (used.to(torch.int32) << torch.arange(N_DIMS, dtype=torch.int32)).sum(
         dim=1).to(torch.int32)
     return MfmaPolicy(b_pack, cards, secrets, tile_dims, R)
+
+
+# ---- compact job descriptors ------------------------------------------------
+# K1 can only be affected by the set dimensions some rule constrains (the
+# union of tile_dims; the rule scan skips every other dimension), so a batch
+# staged for the MFMA K1 needs one int64 column per LIVE dimension instead of
+# the nine words (plus the MCP words the MFMA path never reads) of the full
+# JobBatch layout. The live set is a property of the compiled policy: it is
+# derived here from the MfmaPolicy and has to be derived again whenever the
+# policy is packed again.
+COL_ABSENT = 0xF  # nibble of a dimension that has no column
+
+
+def live_dims(mp: MfmaPolicy) -> List[int]:
+    """Dimensions (0..8: the 7 any-of, then the 2 all-of) some rule tile
+    constrains, ascending. Their count is L, the width of a compact row."""
+    union = 0
+    for v in mp.tile_dims.cpu().tolist():
+        union |= int(v)
+    return [d for d in range(N_DIMS) if (union >> d) & 1]
+
+
+def col_map(live: Sequence[int]) -> int:
+    """Packed d -> column map the compact K1 takes by value: 4 bits per
+    dimension (dimension d at bits 4d..4d+3), COL_ABSENT where d is not live.
+    Columns follow `live`, which must be ascending."""
+    live = list(live)
+    assert live == sorted(set(live)) and all(0 <= d < N_DIMS for d in live), live
+    m = 0
+    for d in range(N_DIMS):
+        m |= (live.index(d) if d in live else COL_ABSENT) << (4 * d)
+    return m
+
+
+def col_of(live: Sequence[int], d: int) -> int:
+    """Column of dimension d in a compact row, -1 if d is not live."""
+    live = list(live)
+    return live.index(d) if d in live else -1
+
+
+def gather_live_cols(jobs: JobBatch, live: Sequence[int]) -> torch.Tensor:
+    """Full-layout batch -> compact rows [J, L] int64 (1-word vocab)."""
+    assert jobs.any_bits.shape[2] == 1, "compact rows need the 1-word vocab"
+    job_bits = torch.cat([jobs.any_bits, jobs.all_bits], dim=1)[:, :, 0]  # [J, 9]
+    idx = torch.tensor(list(live), dtype=torch.int64, device=job_bits.device)
+    return job_bits.index_select(1, idx).contiguous()
 
 
 def pack_jobs_mfma(jobs: JobBatch) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -6,7 +6,12 @@ graph replay, result copy enqueue) with no encode and no harvest wait in the
 way. The device legs (kernels, H2D/D2H copies) come from rocprofv3 traces.
 
 Run on a GPU box; prints one JSON line. Works on trees with or without the
-one-call stamped encoder and the fused result block."""
+one-call stamped encoder, the fused result block and compact descriptor
+staging. Where the pipeline has compact staging it measures the path e2e_run
+takes (compact by default); `--full-layout` builds the pipeline with
+compact_staging=False and measures the full-layout path instead.
+
+  python tools/e2e_legs.py [reps] [--full-layout]"""
 import json
 import statistics
 import sys
@@ -22,23 +27,38 @@ from cordum_amd.utils.threads import cap_torch_threads
 
 
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 400
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    full_layout = "--full-layout" in sys.argv[1:]
+    reps = int(args[0]) if args else 400
     cap_torch_threads()
     dev = torch.device("cuda:0")
-    pipe = DevicePipeline(device=dev, batch_size=16384, n_local_workers=1000,
-                          n_rules=1024, n_batches=2, mfma_pack_on_device=True)
+    kw = dict(device=dev, batch_size=16384, n_local_workers=1000,
+              n_rules=1024, n_batches=2, mfma_pack_on_device=True)
+    import inspect
+
+    if "compact_staging" in inspect.signature(DevicePipeline.__init__).parameters:
+        kw["compact_staging"] = False if full_layout else None
+    pipe = DevicePipeline(**kw)
     pipe.e2e_run(8)  # allocates the staging rings, captures the graphs
     torch.cuda.synchronize(dev)
     B, W = pipe.B, pipe.payload_words
     ext = pipe.ext
     stamped = hasattr(pipe._e2e_encs[0], "fresh_stamped")
     nhost = len(pipe._e2e_hosts2)
+    # what e2e_run stages and replays on this pipeline
+    compact = bool(getattr(pipe, "_compact", False))
+    dev_bufs = pipe.compact_bufs if compact else pipe.batch_bufs
+    host_bufs = pipe._e2e_cbufs if compact else pipe._e2e_host_bufs
+    graphs = pipe._cgraphs if compact else pipe._graphs
 
     def encode(s, threads):
         hb = pipe._e2e_hosts2[s % nhost]
         enc = pipe._e2e_encs[s % nhost]
         payload = pipe._e2e_payloads[s % len(pipe._e2e_payloads)]
-        if stamped:
+        if compact:
+            enc.fresh_compact(pipe._e2e_ccols[s % nhost], s, ext, pipe._e2e_ccolumns,
+                              payload, W, threads=threads)
+        elif stamped:
             enc.fresh_stamped(hb, s, ext, payload, W, threads=threads)
         else:
             enc.fresh_fast(hb, s, ext)
@@ -49,7 +69,8 @@ def main():
     gc.collect()
     gc.freeze()
     gc.disable()
-    out = {"stamped_encoder": stamped, "reps": reps}
+    out = {"stamped_encoder": stamped, "reps": reps, "compact_staging": compact,
+           "live_dims": list(getattr(pipe, "_live", [])) if compact else None}
     for threads in ((1, 2) if stamped else (1,)):
         ts = []
         for s in range(reps):
@@ -80,14 +101,13 @@ def main():
                     # harvest here, order the restage behind it on the device
                     # (one extra event wait per step, counted in the figure)
                     pipe._e2e_copy_stream.wait_event(pipe._e2e_ev[slot])
-                pipe.batch_bufs[slot].copy_(pipe._e2e_host_bufs[s % nhost],
-                                            non_blocking=True)
+                dev_bufs[slot].copy_(host_bufs[s % nhost], non_blocking=True)
                 pipe.payloads[slot].copy_(
                     pipe._e2e_payloads[s % len(pipe._e2e_payloads)],
                     non_blocking=True)
                 pipe._e2e_in_ev[slot].record(pipe._e2e_copy_stream)
             main_stream.wait_event(pipe._e2e_in_ev[slot])
-            pipe._graphs[slot].replay()
+            graphs[slot].replay()
             if fused_out:
                 pipe._e2e_out_blocks[slot].copy_(pipe._res_block, non_blocking=True)
             else:
@@ -113,7 +133,7 @@ def main():
         return round(e0.elapsed_time(e1) * 1e3 / n, 1)
 
     def h2d(s):
-        pipe.batch_bufs[s % nslots].copy_(pipe._e2e_host_bufs[s % nhost], non_blocking=True)
+        dev_bufs[s % nslots].copy_(host_bufs[s % nhost], non_blocking=True)
         pipe.payloads[s % nslots].copy_(pipe._e2e_payloads[s % len(pipe._e2e_payloads)],
                                         non_blocking=True)
 
@@ -126,12 +146,25 @@ def main():
             pipe._e2e_out_dec[slot].copy_(pipe.out_decision, non_blocking=True)
             pipe._e2e_out_counts[slot].copy_(pipe._counts, non_blocking=True)
 
-    h2d_bytes = pipe.batch_bufs[0].numel() + pipe.payloads[0].numel() * 4
+    def h2d_desc(s):
+        dev_bufs[s % nslots].copy_(host_bufs[s % nhost], non_blocking=True)
+
+    def h2d_payload(s):
+        pipe.payloads[s % nslots].copy_(pipe._e2e_payloads[s % len(pipe._e2e_payloads)],
+                                        non_blocking=True)
+
+    desc_bytes = dev_bufs[0].numel()
+    h2d_bytes = desc_bytes + pipe.payloads[0].numel() * 4
+    out["descriptor_bytes_per_step"] = desc_bytes
+    out["descriptor_bytes_per_job"] = round(desc_bytes / B, 2)
     out["h2d_bytes_per_step"] = h2d_bytes
     out["h2d_us_per_step"] = [timed(h2d) for _ in range(3)]
     out["h2d_GBps"] = round(h2d_bytes / (min(out["h2d_us_per_step"]) * 1e-6) / 1e9, 1)
+    # the two copies of a step on their own: what each costs beyond its bytes
+    out["h2d_descriptors_us"] = [timed(h2d_desc) for _ in range(3)]
+    out["h2d_payload_us"] = [timed(h2d_payload) for _ in range(3)]
     out["d2h_us_per_step"] = [timed(d2h) for _ in range(3)]
-    out["graph_replay_us_per_step"] = [timed(lambda s: pipe._graphs[s % nslots].replay())
+    out["graph_replay_us_per_step"] = [timed(lambda s: graphs[s % nslots].replay())
                                        for _ in range(3)]
     out["submit_us_per_step"] = [round(r[0], 1) for r in runs]
     out["submit_plus_drain_us_per_step"] = [round(r[1], 1) for r in runs]
