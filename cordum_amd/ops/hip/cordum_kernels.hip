@@ -857,19 +857,19 @@ __device__ __forceinline__ unsigned int wf_mix(unsigned int x) {
 // failures are injected by a hash of the child's (tag, emission ordinal) —
 // independent of packing order, so every backend agrees). Flagged entries
 // are redeliveries whose tag/seq live in the rq_prev carries.
-__global__ __launch_bounds__(BLOCK) void wf_apply_kernel(
-    const int* __restrict__ send_slots,       // [world*cap]
-    const int* __restrict__ send_cnt,         // [world]
-    const int* __restrict__ child_tag,        // [CB]
-    const int* __restrict__ child_seq,        // [CB]
-    const int* __restrict__ rq_prev_tag,      // [rq_cap]
-    const int* __restrict__ rq_prev_seq,      // [rq_cap]
-    int* __restrict__ children_done,          // [NR*64]
-    int* __restrict__ children_fail,          // [NR*64]
-    int* __restrict__ children_out,           // [NR*64]
+// One body for wf_apply and wf_apply_out (device conditions): OUT only adds
+// the step-output accumulation, so the counters of the two cannot drift.
+template <bool OUT>
+__device__ __forceinline__ void wf_apply_one(
+    const int i,
+    const int* __restrict__ send_slots, const int* __restrict__ send_cnt,
+    const int* __restrict__ child_tag, const int* __restrict__ child_seq,
+    const int* __restrict__ rq_prev_tag, const int* __restrict__ rq_prev_seq,
+    int* __restrict__ children_done, int* __restrict__ children_fail,
+    int* __restrict__ children_out,
+    const unsigned int* __restrict__ sums_back, unsigned int* __restrict__ step_out,
     int fail_ppt, int drop_ppt, int cap, int world)
 {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= world * cap) return;
     if ((i % cap) >= min(send_cnt[i / cap], cap)) return;
     const int sslot = send_slots[i];
@@ -882,9 +882,49 @@ __global__ __launch_bounds__(BLOCK) void wf_apply_kernel(
     if ((int)(hd % 1000u) < drop_ppt) return;
     const unsigned int h = wf_mix((unsigned int)tag * 2654435761u
                                   ^ (unsigned int)seq * 40503u);
-    if ((int)(h % 1000u) < fail_ppt) atomicAdd(&children_fail[tag], 1);
-    else atomicAdd(&children_done[tag], 1);
+    if ((int)(h % 1000u) < fail_ppt) {
+        atomicAdd(&children_fail[tag], 1);
+    } else {
+        atomicAdd(&children_done[tag], 1);
+        // the step's output: wraparound sum of its succeeded children's
+        // result words (addition mod 2^32 commutes: order cannot matter)
+        if (OUT) atomicAdd(&step_out[tag], sums_back[i]);
+    }
     atomicSub(&children_out[tag], 1);
+}
+
+__global__ __launch_bounds__(BLOCK) void wf_apply_kernel(
+    const int* __restrict__ send_slots,       // [world*cap]
+    const int* __restrict__ send_cnt,         // [world]
+    const int* __restrict__ child_tag,        // [CB]
+    const int* __restrict__ child_seq,        // [CB]
+    const int* __restrict__ rq_prev_tag,      // [rq_cap]
+    const int* __restrict__ rq_prev_seq,      // [rq_cap]
+    int* __restrict__ children_done,          // [NR*64]
+    int* __restrict__ children_fail,          // [NR*64]
+    int* __restrict__ children_out,           // [NR*64]
+    int fail_ppt, int drop_ppt, int cap, int world)
+{
+    wf_apply_one<false>(blockIdx.x * BLOCK + threadIdx.x, send_slots, send_cnt, child_tag,
+                        child_seq, rq_prev_tag, rq_prev_seq, children_done, children_fail,
+                        children_out, nullptr, nullptr, fail_ppt, drop_ppt, cap, world);
+}
+
+// wf_apply with step outputs (device conditions): sums_back[i] is the echo
+// checksum of send entry i, step_out[tag] the output word of step tag
+__global__ __launch_bounds__(BLOCK) void wf_apply_out_kernel(
+    const int* __restrict__ send_slots, const int* __restrict__ send_cnt,
+    const int* __restrict__ child_tag, const int* __restrict__ child_seq,
+    const int* __restrict__ rq_prev_tag, const int* __restrict__ rq_prev_seq,
+    int* __restrict__ children_done, int* __restrict__ children_fail,
+    int* __restrict__ children_out,
+    const unsigned int* __restrict__ sums_back,   // [world*cap]
+    unsigned int* __restrict__ step_out,          // [NR*64]
+    int fail_ppt, int drop_ppt, int cap, int world)
+{
+    wf_apply_one<true>(blockIdx.x * BLOCK + threadIdx.x, send_slots, send_cnt, child_tag,
+                       child_seq, rq_prev_tag, rq_prev_seq, children_done, children_fail,
+                       children_out, sums_back, step_out, fail_ppt, drop_ppt, cap, world);
 }
 
 // dead-letter application: entries dropped by the requeue ring (max-deliver
@@ -1596,6 +1636,223 @@ __global__ __launch_bounds__(BLOCK) void wf_settle_kernel(
         const unsigned long long nr = part[1][0] + part[1][1] + part[1][2] + part[1][3];
         if (nl) atomicAdd(timeout_count, nl);
         if (nr) atomicAdd(retry_count, nr);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K3-WF conditions decided on the device: wf_cond_eval / wf_child_payload
+// ---------------------------------------------------------------------------
+// A step may carry a predicate over the run's input words and the output
+// words of steps it (transitively) depends on. Predicates are held per
+// template, one 16-byte record (code, a, b, imm) per step:
+//   code bits 0..3   op: 0 none, 1 EQ, 2 NE, 3 LT, 4 LE, 5 GT, 6 GE,
+//                    7 TRUTHY (lhs != 0, rhs ignored)
+//        bit  4      negate the result
+//        bits 8..9   lhs kind: 1 INPUT, 2 OUT
+//        bits 12..13 rhs kind: 0 IMM, 1 INPUT, 2 OUT
+//   a, b             lhs / rhs index (input word, or step), imm the immediate
+// All comparisons are signed 32-bit. tmpl_cond_mask[t] bit s = step s of
+// template t has a predicate. The host validates the records; the kernel
+// still reads an operand whose index is outside its row as 0.
+#define WFC_EQ 1
+#define WFC_NE 2
+#define WFC_LT 3
+#define WFC_LE 4
+#define WFC_GT 5
+#define WFC_GE 6
+#define WFC_TRUTHY 7
+
+__device__ __forceinline__ int wf_cond_operand(int kind, int idx, int imm,
+                                               const int* __restrict__ in_row, int IW,
+                                               const int* __restrict__ out_row)
+{
+    if (kind == 1) return (unsigned)idx < (unsigned)IW ? in_row[idx] : 0;
+    if (kind == 2) return (unsigned)idx < 64u ? out_row[idx] : 0;
+    return imm;
+}
+
+__device__ __forceinline__ bool wf_cond_value(const int4 rec,
+                                              const int* __restrict__ in_row, int IW,
+                                              const int* __restrict__ out_row)
+{
+    const int code = rec.x;
+    const int lk = (code >> 8) & 3;
+    const int lhs = wf_cond_operand(lk == 0 ? 3 : lk, rec.y, 0, in_row, IW, out_row);
+    const int rhs = wf_cond_operand((code >> 12) & 3, rec.z, rec.w, in_row, IW, out_row);
+    bool v = false;
+    switch (code & 15) {
+    case WFC_EQ: v = lhs == rhs; break;
+    case WFC_NE: v = lhs != rhs; break;
+    case WFC_LT: v = lhs < rhs; break;
+    case WFC_LE: v = lhs <= rhs; break;
+    case WFC_GT: v = lhs > rhs; break;
+    case WFC_GE: v = lhs >= rhs; break;
+    case WFC_TRUTHY: v = lhs != 0; break;
+    }
+    return v != (((code >> 4) & 1) != 0);
+}
+
+// wf_cond_eval runs directly before wf_sweep. Layout as wf_settle: 4 lanes per
+// row, 16 steps (one 16-byte state load) per lane, 64 rows per block. A row
+// is looked at only if it is LIVE, run_active is set and run_tmpl is inside
+// the table; the four lanes OR their shares of `satisfied` (SUCCEEDED or
+// SKIPPED, as the sweep) and `pending` with two xor-shuffles. A wave in which
+// no row has a PENDING step with a predicate does nothing more and writes
+// nothing. A PENDING predicate step whose deps are satisfied is evaluated:
+//   CONDITION  its bit in cond_bits[run] is set or cleared and step_out is
+//              1 or 0; the sweep of this tick commits it, unchanged
+//   guard      true: the step stays PENDING; false: it becomes SKIPPED
+// A step skipped here satisfies its dependents in the sweep of this same
+// tick, so the pass repeats (wave-uniform) until no guard turned false:
+// otherwise the sweep would dispatch a dependent whose own guard was never
+// looked at. Each step is evaluated at most once per launch. next_ready is
+// not consulted: operands are final and inputs constant, so a step that
+// returns to PENDING (retry, for_each window) evaluates the same again.
+// cond_bits[run] is written once per row by lane q == 0; a lane stores its 16
+// state bytes back only if one changed; cond_counts (true, false) gets at
+// most one atomic add per counter and block.
+__global__ __launch_bounds__(BLOCK) void wf_cond_eval_kernel(
+    unsigned char* __restrict__ step_state,         // [NR*64]
+    const long long* __restrict__ deps_mask,        // [NR*64]
+    const unsigned char* __restrict__ step_kind,    // [NR*64]
+    const unsigned char* __restrict__ run_life,     // [NR]
+    const unsigned char* __restrict__ run_active,   // [NR]
+    const int* __restrict__ run_tmpl,               // [NR]
+    const int4* __restrict__ tmpl_cond,             // [TC*64]
+    const unsigned long long* __restrict__ tmpl_cond_mask, // [TC]
+    const int* __restrict__ run_input,              // [NR*IW]
+    int* __restrict__ step_out,                     // [NR*64]
+    unsigned long long* __restrict__ cond_bits,     // [NR]
+    unsigned long long* __restrict__ cond_counts,   // [2] true, false
+    int NR, int TC, int IW)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int r = t >> 2;                           // 4 lanes per row
+    const int q = t & 3;                            // steps 16q .. 16q+15
+    const size_t off = (size_t)r * 64 + (size_t)q * 16;
+    bool look = r < NR && run_life[r] == WFL_LIVE && run_active[r] != 0;
+    int tmpl = 0;
+    if (look) {
+        tmpl = run_tmpl[r];
+        look = tmpl >= 0 && tmpl < TC;
+    }
+    uint4 st = make_uint4(0u, 0u, 0u, 0u);
+    unsigned long long cmask = 0ull;
+    if (look) {
+        st = *reinterpret_cast<const uint4*>(step_state + off);
+        cmask = tmpl_cond_mask[tmpl];
+    }
+    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
+    unsigned nw[4] = {sw[0], sw[1], sw[2], sw[3]};
+    unsigned pend = 0u;                             // bit j: step 16q+j is PENDING
+    if (look) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            pend |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_PENDING) << j;
+    }
+    // this lane's PENDING steps that carry a predicate and are not yet decided
+    unsigned todo = pend & (unsigned)(cmask >> (q * 16)) & 0xffffu;
+    unsigned long long setm = 0ull, clrm = 0ull;
+    unsigned n_true = 0u, n_false = 0u;
+    bool again = __any(todo != 0u);                 // wave-uniform
+    while (again) {
+        unsigned sat16 = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned b = (nw[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+            sat16 |= (unsigned)(b == WFS_SUCCEEDED || b == WFS_SKIPPED) << j;
+        }
+        unsigned long long sat = (unsigned long long)sat16 << (q * 16);
+        sat |= __shfl_xor(sat, 1, WAVE);
+        sat |= __shfl_xor(sat, 2, WAVE);
+        bool skipped = false;
+#pragma unroll 1
+        for (unsigned f = todo; f != 0u; f &= f - 1u) {
+            const int j = __ffs((int)f) - 1;
+            const size_t i = off + j;
+            if (((unsigned long long)deps_mask[i] & ~sat) != 0ull) continue;
+            todo &= ~(1u << j);
+            const bool v = wf_cond_value(tmpl_cond[(size_t)tmpl * 64 + q * 16 + j],
+                                         run_input + (size_t)r * IW, IW,
+                                         step_out + (size_t)r * 64);
+            n_true += v ? 1u : 0u;
+            n_false += v ? 0u : 1u;
+            if (step_kind[i] == WFK_CONDITION) {
+                const unsigned long long bit = 1ull << (q * 16 + j);
+                if (v) setm |= bit; else clrm |= bit;
+                step_out[i] = v ? 1 : 0;
+            } else if (!v) {
+                const int sft = (j & 3) * 8;
+                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | ((unsigned)WFS_SKIPPED << sft);
+                skipped = true;
+            }
+        }
+        // only a step skipped in this pass can have made another one ready
+        again = __any(skipped) && __any(todo != 0u);
+    }
+    unsigned long long acc = 0ull;
+    if (__any((setm | clrm) != 0ull || n_true + n_false != 0u)) {   // wave-uniform
+        setm |= __shfl_xor(setm, 1, WAVE);
+        setm |= __shfl_xor(setm, 2, WAVE);
+        clrm |= __shfl_xor(clrm, 1, WAVE);
+        clrm |= __shfl_xor(clrm, 2, WAVE);
+        if (q == 0 && (setm | clrm) != 0ull)
+            cond_bits[r] = (cond_bits[r] & ~clrm) | setm;
+        if (nw[0] != sw[0] || nw[1] != sw[1] || nw[2] != sw[2] || nw[3] != sw[3])
+            *reinterpret_cast<uint4*>(step_state + off) =
+                make_uint4(nw[0], nw[1], nw[2], nw[3]);
+        // wave totals in one butterfly: two 32-bit fields (each <= 1024)
+        acc = (unsigned long long)n_true | (unsigned long long)n_false << 32;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) acc += __shfl_xor(acc, d, WAVE);
+    }
+    __shared__ unsigned long long part[BLOCK / WAVE];
+    if (threadIdx.x % WAVE == 0) part[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
+        const unsigned long long nt = sum & 0xffffffffull, nf = sum >> 32;
+        if (nt) atomicAdd(&cond_counts[0], nt);
+        if (nf) atomicAdd(&cond_counts[1], nf);
+    }
+}
+
+// wf_child_payload runs after wf_expand and writes the payload row of every
+// child emitted this tick (arena slots 0 .. min(child_count, CB) - 1):
+//   words [0, IW)  the run's input words
+//   word  IW       the child's emission ordinal (child_seq)
+//   word  IW + 1   its step index
+//   the rest       zero
+// so a child's echo checksum is a function of (run input, step, ordinal) and
+// of nothing else. The grid is fixed (graph capture), one wave per row and
+// striding over the rows; the count is read from memory and nothing past it
+// is touched.
+__global__ __launch_bounds__(BLOCK) void wf_child_payload_kernel(
+    const int* __restrict__ child_tag,              // [CB]
+    const int* __restrict__ child_seq,              // [CB]
+    const int* __restrict__ child_count,            // [1]
+    const int* __restrict__ run_input,              // [NR*IW]
+    int* __restrict__ child_payload,                // [CB*W]
+    int CB, int NR, int IW, int W)
+{
+    const int n = min(max(*child_count, 0), CB);
+    const int lane = threadIdx.x % WAVE;
+    const int nwaves = (int)gridDim.x * (BLOCK / WAVE);
+    // one wave per row: tag and ordinal are wave-uniform loads, the row is
+    // written as consecutive words
+    for (int c = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE; c < n; c += nwaves) {
+        const int tag = child_tag[c];
+        const int seq = child_seq[c];
+        const int run = tag >> 6;
+        const bool known = (unsigned)run < (unsigned)NR;
+        int* __restrict__ row = child_payload + (size_t)c * W;
+        for (int k = lane; k < W; k += WAVE) {
+            int v = 0;
+            if (k < IW) v = known ? run_input[(size_t)run * IW + k] : 0;
+            else if (k == IW) v = seq;
+            else if (k == IW + 1) v = tag & 63;
+            row[k] = v;
+        }
     }
 }
 
@@ -3809,6 +4066,104 @@ void wf_settle(torch::Tensor step_state, torch::Tensor step_attempts,
         (unsigned long long*)retry_count.data_ptr<int64_t>(), (int)NR, (int)TC);
 }
 
+// one predicate pass on the current stream (inside the tick, directly before
+// wf_sweep); tmpl_cond is [TC*64*4], tmpl_cond_mask [TC], run_input [NR*IW]
+void wf_cond_eval(torch::Tensor step_state, torch::Tensor deps_mask, torch::Tensor step_kind,
+                  torch::Tensor run_life, torch::Tensor run_active, torch::Tensor run_tmpl,
+                  torch::Tensor tmpl_cond, torch::Tensor tmpl_cond_mask,
+                  torch::Tensor run_input, torch::Tensor step_out, torch::Tensor cond_bits,
+                  torch::Tensor cond_counts, int64_t input_words)
+{
+    const int64_t NR = run_life.numel();
+    const int64_t TC = tmpl_cond_mask.numel();
+    const int64_t IW = input_words;
+    if (NR <= 0) return;
+    TORCH_CHECK(step_state.numel() == NR * 64 && deps_mask.numel() == NR * 64
+                && step_kind.numel() == NR * 64 && run_active.numel() == NR
+                && run_tmpl.numel() == NR && step_out.numel() == NR * 64
+                && cond_bits.numel() == NR, "wf_cond_eval: table sizes disagree");
+    TORCH_CHECK(IW >= 1 && IW <= 32 && run_input.numel() == NR * IW,
+                "wf_cond_eval: run_input needs NR*input_words words, 1 <= input_words <= 32");
+    TORCH_CHECK(TC >= 1 && tmpl_cond.numel() == TC * 64 * 4 && TC * 64 <= (int64_t)INT_MAX,
+                "wf_cond_eval: predicate tables need TC*64*4 and TC words, TC >= 1");
+    TORCH_CHECK(cond_counts.numel() >= 2, "wf_cond_eval: counters need two words");
+    TORCH_CHECK(step_state.is_contiguous() && deps_mask.is_contiguous()
+                && step_kind.is_contiguous() && run_life.is_contiguous()
+                && run_active.is_contiguous() && run_tmpl.is_contiguous()
+                && tmpl_cond.is_contiguous() && tmpl_cond_mask.is_contiguous()
+                && run_input.is_contiguous() && step_out.is_contiguous()
+                && cond_bits.is_contiguous(), "wf_cond_eval: tables must be contiguous");
+    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_cond_eval: table too large");
+    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
+                && (uintptr_t)tmpl_cond.data_ptr<int>() % 16 == 0,
+                "wf_cond_eval: states and predicate records must be 16-byte aligned");
+    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(wf_cond_eval_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        step_state.data_ptr<uint8_t>(), (const long long*)deps_mask.data_ptr<int64_t>(),
+        step_kind.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
+        run_active.data_ptr<uint8_t>(), run_tmpl.data_ptr<int>(),
+        reinterpret_cast<const int4*>(tmpl_cond.data_ptr<int>()),
+        (const unsigned long long*)tmpl_cond_mask.data_ptr<int64_t>(),
+        run_input.data_ptr<int>(), step_out.data_ptr<int>(),
+        (unsigned long long*)cond_bits.data_ptr<int64_t>(),
+        (unsigned long long*)cond_counts.data_ptr<int64_t>(), (int)NR, (int)TC, (int)IW);
+}
+
+// payload rows of the children emitted this tick (after wf_expand); the grid
+// is fixed, the count is read on the device
+void wf_child_payload(torch::Tensor child_tag, torch::Tensor child_seq,
+                      torch::Tensor child_count, torch::Tensor run_input,
+                      torch::Tensor child_payload, int64_t input_words, int64_t payload_words)
+{
+    const int64_t CB = child_tag.numel();
+    const int64_t IW = input_words, W = payload_words;
+    if (CB <= 0) return;
+    TORCH_CHECK(IW >= 1 && IW <= 32 && W >= IW + 2,
+                "wf_child_payload: needs 1 <= input_words <= 32, payload_words >= input_words + 2");
+    TORCH_CHECK(child_seq.numel() == CB && child_count.numel() >= 1
+                && child_payload.numel() == CB * W && run_input.numel() % IW == 0
+                && run_input.numel() >= IW, "wf_child_payload: table sizes disagree");
+    TORCH_CHECK(CB * W <= (int64_t)INT_MAX && run_input.numel() <= (int64_t)INT_MAX,
+                "wf_child_payload: arena too large");
+    TORCH_CHECK(child_tag.is_contiguous() && child_seq.is_contiguous()
+                && run_input.is_contiguous() && child_payload.is_contiguous(),
+                "wf_child_payload: tables must be contiguous");
+    const int64_t NR = run_input.numel() / IW;
+    // 4 rows per block and pass; 2048 blocks fill the device at 8 waves/SIMD
+    const int blocks = (int)std::min<int64_t>((CB + BLOCK / WAVE - 1) / (BLOCK / WAVE), 2048);
+    hipLaunchKernelGGL(wf_child_payload_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        child_tag.data_ptr<int>(), child_seq.data_ptr<int>(), child_count.data_ptr<int>(),
+        run_input.data_ptr<int>(), child_payload.data_ptr<int>(),
+        (int)CB, (int)NR, (int)IW, (int)W);
+}
+
+// wf_apply plus the step outputs: sums_back is [world*cap], step_out [NR*64]
+void wf_apply_out(torch::Tensor send_slots, torch::Tensor send_cnt, torch::Tensor child_tag,
+                  torch::Tensor child_seq, torch::Tensor rq_prev_tag, torch::Tensor rq_prev_seq,
+                  torch::Tensor children_done,
+                  torch::Tensor children_fail, torch::Tensor children_out,
+                  torch::Tensor sums_back, torch::Tensor step_out,
+                  int64_t fail_ppt, int64_t drop_ppt, int64_t cap, int64_t world)
+{
+    const int n = (int)(world * cap);
+    TORCH_CHECK(send_slots.numel() >= n && sums_back.numel() >= n && send_cnt.numel() >= world,
+                "wf_apply_out: send tables need world*cap entries");
+    TORCH_CHECK(step_out.numel() == children_done.numel()
+                && children_fail.numel() == children_done.numel()
+                && children_out.numel() == children_done.numel(),
+                "wf_apply_out: table sizes disagree");
+    TORCH_CHECK(sums_back.is_contiguous() && step_out.is_contiguous(),
+                "wf_apply_out: tables must be contiguous");
+    const int blocks = (n + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(wf_apply_out_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        send_slots.data_ptr<int>(), send_cnt.data_ptr<int>(), child_tag.data_ptr<int>(),
+        child_seq.data_ptr<int>(), rq_prev_tag.data_ptr<int>(), rq_prev_seq.data_ptr<int>(),
+        children_done.data_ptr<int>(),
+        children_fail.data_ptr<int>(), children_out.data_ptr<int>(),
+        (const unsigned int*)sums_back.data_ptr<int>(), (unsigned int*)step_out.data_ptr<int>(),
+        (int)fail_ppt, (int)drop_ppt, (int)cap, (int)world);
+}
+
 // one page of open holds, three launches on the current stream. list is
 // [count, pad x3 | cap records of 4 words]; list_mask / blk_scan are
 // caller-owned workspaces ([NR] int64, [nblk+1] int32, nblk = ceil(NR/256))
@@ -4240,6 +4595,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_journal", &wf_journal, "K3-WF step-transition journal pass (observer)");
     m.def("wf_hold_scan", &wf_hold_scan, "K3-WF approval hold scan (open / expire / close holds)");
     m.def("wf_settle", &wf_settle, "K3-WF per-step-policy timeout + commit pass (replaces the scan/commit pair)");
+    m.def("wf_cond_eval", &wf_cond_eval, "K3-WF predicate pass before the sweep (condition bits, guards -> SKIPPED)");
+    m.def("wf_child_payload", &wf_child_payload, "K3-WF payload rows of the children emitted this tick");
+    m.def("wf_apply_out", &wf_apply_out, "K3-WF child result application with step outputs");
     m.def("wf_hold_list", &wf_hold_list, "K3-WF ordered page of open approval holds");
     m.def("wf_decide", &wf_decide, "K3-WF generation-checked approval decisions");
     m.def("materialize_rq_payload", &materialize_rq_payload, "copy requeued payload rows into the rq arena");

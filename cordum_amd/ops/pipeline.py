@@ -388,6 +388,21 @@ class _RefOps:
 
         wf_settle_ref(*a)
 
+    def wf_cond_eval(self, *a):
+        from .reference import wf_cond_eval_ref
+
+        wf_cond_eval_ref(*a)
+
+    def wf_child_payload(self, *a):
+        from .reference import wf_child_payload_ref
+
+        wf_child_payload_ref(*a)
+
+    def wf_apply_out(self, *a):
+        from .reference import wf_apply_out_ref
+
+        wf_apply_out_ref(*a)
+
     def wf_hold_list(self, st, rl, ra, rg, hm, ht, hg, cursor, lm, bs, out):
         from .reference import wf_hold_list_ref
 

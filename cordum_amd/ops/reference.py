@@ -435,7 +435,8 @@ def wf_drop_hash(tag: int, seq: int) -> int:
 
 def wf_apply_ref(send_slots, send_cnt, child_tag, child_seq, rq_prev_tag,
                  rq_prev_seq, children_done, children_fail, children_out,
-                 fail_ppt: int, drop_ppt: int, cap: int, world: int):
+                 fail_ppt: int, drop_ppt: int, cap: int, world: int,
+                 sums_back=None, step_out=None):
     for r in range(world):
         for e in range(min(int(send_cnt[r]), cap)):
             i = r * cap + e
@@ -448,6 +449,9 @@ def wf_apply_ref(send_slots, send_cnt, child_tag, child_seq, rq_prev_tag,
                 children_fail[tag] += 1
             else:
                 children_done[tag] += 1
+                if step_out is not None:    # wf_apply_out: the step's output word
+                    v = (int(step_out[tag]) + int(sums_back[i])) & 0xFFFFFFFF
+                    step_out[tag] = v - (1 << 32) if v >= (1 << 31) else v
             children_out[tag] -= 1
 
 
@@ -879,3 +883,121 @@ def wf_settle_ref(step_state, step_attempts, children_todo, children_out,
                 step_state[i] = WFS_SUCCEEDED
     timeout_count[0] += lost_sum
     retry_count[0] += retry_sum
+
+
+# -- K3-WF conditions decided on the device --------------------------------------
+# Predicate record (code, a, b, imm), see the kernel section of the same name:
+# code bits 0..3 op, bit 4 negate, bits 8..9 lhs kind, bits 12..13 rhs kind.
+WFC_EQ, WFC_NE, WFC_LT, WFC_LE, WFC_GT, WFC_GE, WFC_TRUTHY = 1, 2, 3, 4, 5, 6, 7
+WFC_NEGATE = 1 << 4
+WFC_IMM, WFC_INPUT, WFC_OUT = 0, 1, 2
+
+
+def wf_cond_value_ref(rec, in_row, out_row) -> bool:
+    """Value of one predicate record over a run's input words and step output
+    words; comparisons are signed 32-bit, an operand index outside its row
+    reads as 0."""
+    code, a, b, imm = (int(x) for x in rec)
+
+    def operand(kind, idx, lit):
+        if kind == WFC_INPUT:
+            return int(in_row[idx]) if 0 <= idx < len(in_row) else 0
+        if kind == WFC_OUT:
+            return int(out_row[idx]) if 0 <= idx < 64 else 0
+        return lit
+
+    lk = (code >> 8) & 3
+    lhs = operand(lk, a, 0) if lk else 0
+    rhs = operand((code >> 12) & 3, b, imm)
+    op = code & 15
+    v = {WFC_EQ: lhs == rhs, WFC_NE: lhs != rhs, WFC_LT: lhs < rhs,
+         WFC_LE: lhs <= rhs, WFC_GT: lhs > rhs, WFC_GE: lhs >= rhs,
+         WFC_TRUTHY: lhs != 0}.get(op, False)
+    return v != bool(code & WFC_NEGATE)
+
+
+def wf_cond_eval_ref(step_state, deps_mask, step_kind, run_life, run_active,
+                     run_tmpl, tmpl_cond, tmpl_cond_mask, run_input, step_out,
+                     cond_bits, cond_counts, input_words: int):
+    """The predicate pass before the sweep. Per LIVE, active row with a
+    template id inside the table: every PENDING step that carries a predicate
+    and whose deps are satisfied (SUCCEEDED or SKIPPED) is evaluated once. A
+    CONDITION step gets its bit in cond_bits set or cleared and step_out 1 or
+    0; any other step stays PENDING if true and becomes SKIPPED if false. A
+    step skipped here can satisfy another one's deps, so the row repeats until
+    no guard turned false."""
+    NR = int(run_life.shape[0])
+    TC = int(tmpl_cond_mask.shape[0])
+    IW = int(input_words)
+    st = step_state.view(NR, 64)
+    look = ((run_life[:NR] == WFL_LIVE) & (run_active[:NR] != 0)
+            & (run_tmpl[:NR] >= 0) & (run_tmpl[:NR] < TC))
+    n_true = n_false = 0
+    for r in torch.nonzero(look).flatten().tolist():
+        t = int(run_tmpl[r])
+        cmask = int(tmpl_cond_mask[t]) & _M64
+        todo = [s for s in range(64)
+                if (cmask >> s) & 1 and int(st[r, s]) == WFS_PENDING]
+        if not todo:
+            continue
+        in_row = run_input[r * IW:(r + 1) * IW].tolist()
+        setm = clrm = 0
+        while todo:
+            row = st[r].tolist()
+            sat = sum(1 << s for s in range(64) if row[s] in (WFS_SUCCEEDED, WFS_SKIPPED))
+            skipped, left = False, []
+            for s in todo:
+                i = r * 64 + s
+                if (int(deps_mask[i]) & _M64) & ~sat:
+                    left.append(s)
+                    continue
+                v = wf_cond_value_ref(tmpl_cond[(t * 64 + s) * 4:(t * 64 + s) * 4 + 4].tolist(),
+                                      in_row, step_out[r * 64:r * 64 + 64].tolist())
+                n_true += int(v)
+                n_false += int(not v)
+                if int(step_kind[i]) == WFK_CONDITION:
+                    if v:
+                        setm |= 1 << s
+                    else:
+                        clrm |= 1 << s
+                    step_out[i] = int(v)
+                elif not v:
+                    step_state[i] = WFS_SKIPPED
+                    skipped = True
+            todo = left
+            if not skipped:
+                break
+        if setm | clrm:
+            cond_bits[r] = _to_i64(((int(cond_bits[r]) & _M64) & ~clrm) | setm)
+    cond_counts[0] += n_true
+    cond_counts[1] += n_false
+
+
+def wf_child_payload_ref(child_tag, child_seq, child_count, run_input,
+                         child_payload, input_words: int, payload_words: int):
+    """Payload rows of arena slots 0 .. min(child_count, CB) - 1: the run's
+    input words, the child's ordinal, its step index, then zeros."""
+    CB = int(child_tag.shape[0])
+    IW, W = int(input_words), int(payload_words)
+    NR = int(run_input.shape[0]) // IW
+    n = min(max(int(child_count[0]), 0), CB)
+    pl = child_payload.view(-1, W)
+    for c in range(n):
+        tag = int(child_tag[c])
+        run = tag >> 6
+        pl[c].zero_()
+        if 0 <= run < NR:
+            pl[c, :IW] = run_input[run * IW:(run + 1) * IW]
+        pl[c, IW] = int(child_seq[c])
+        pl[c, IW + 1] = tag & 63
+
+
+def wf_apply_out_ref(send_slots, send_cnt, child_tag, child_seq, rq_prev_tag,
+                     rq_prev_seq, children_done, children_fail, children_out,
+                     sums_back, step_out, fail_ppt: int, drop_ppt: int, cap: int,
+                     world: int):
+    """wf_apply_ref, and a child counted as done adds its result word
+    sums_back[i] into step_out[tag], wrapping at 32 bits."""
+    wf_apply_ref(send_slots, send_cnt, child_tag, child_seq, rq_prev_tag,
+                 rq_prev_seq, children_done, children_fail, children_out,
+                 fail_ppt, drop_ppt, cap, world, sums_back, step_out)

@@ -57,6 +57,14 @@ one kernel (wf_settle) stands in for the pair wf_timeout_scan + wf_commit and
 reads each step's constants from its template (see "per-step policy" below).
 With the default `step_policy=False` nothing is allocated and the tick is
 unchanged.
+
+With `device_conditions=True` dynamic mode decides conditions on the device
+from data the run produces: a step may carry a predicate (`StepSpec.when`)
+over the run's input words and the output words of steps it depends on. Three
+kernels join the tick: wf_cond_eval before the sweep, wf_child_payload after
+wf_expand, and wf_apply_out in place of wf_apply (see "conditions decided on
+the device" below). With the default nothing is allocated and the tick is
+unchanged.
 """
 from __future__ import annotations
 
@@ -90,6 +98,25 @@ class RetrySpec:
     cap_ticks: int = 16
 
 
+WFC_EQ, WFC_NE, WFC_LT, WFC_LE, WFC_GT, WFC_GE, WFC_TRUTHY = 1, 2, 3, 4, 5, 6, 7
+_WFC_OPS = {"==": WFC_EQ, "!=": WFC_NE, "<": WFC_LT, "<=": WFC_LE, ">": WFC_GT,
+            ">=": WFC_GE, "truthy": WFC_TRUTHY}
+_I32_MIN, _I32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+@dataclass
+class CondSpec:
+    """Predicate of one step (pipeline with device_conditions): `lhs op rhs`,
+    signed 32-bit. `op` is one of WFC_EQ .. WFC_TRUTHY (or "==", "!=", "<",
+    "<=", ">", ">=", "truthy"); TRUTHY is `lhs != 0` and ignores rhs. An
+    operand is ("input", k) for input word k of the run, ("out", j) for the
+    output word of step j, or (rhs only) an int immediate."""
+    op: object
+    lhs: tuple
+    rhs: object = 0
+    negate: bool = False
+
+
 @dataclass
 class StepSpec:
     kind: int
@@ -103,12 +130,19 @@ class StepSpec:
     # backoff; 0 = the pipeline's timeout_cutoff
     retry: Optional[RetrySpec] = None
     timeout_ticks: int = 0   # ticks until lost children are written off
+    # device_conditions pipelines: on a CONDITION step the predicate decides
+    # the step (`cond` is then ignored); on any other step it is a guard, and
+    # the step is SKIPPED without running when it is false
+    when: Optional[CondSpec] = None
 
 
 @dataclass
 class DagSpec:
     """One workflow DAG (<= 64 steps)."""
     steps: List[StepSpec] = field(default_factory=list)
+    # set by the lowering of a workflow with conditions: the run-input field
+    # names, in the order of the input words they were given
+    input_names: List[str] = field(default_factory=list)
 
     @classmethod
     def fanout_approval(cls, fanout: int = 256) -> "DagSpec":
@@ -169,9 +203,26 @@ class WorkflowPipeline:
         # dynamic mode only: retry / backoff / timeout per step, read from the
         # template by wf_settle (see "per-step policy")
         step_policy: bool = False,
+        # dynamic mode only: predicates over run inputs and step outputs,
+        # decided by wf_cond_eval (see "conditions decided on the device")
+        device_conditions: bool = False,
+        input_words: int = 8,
     ):
         if approvals not in ("auto", "external"):
             raise ValueError("approvals must be 'auto' or 'external'")
+        self.device_conditions = bool(device_conditions)
+        if self.device_conditions:
+            if dynamic_capacity is None:
+                raise ValueError("device_conditions needs dynamic_capacity: the "
+                                 "predicates are held per template")
+            if not 1 <= int(input_words) <= 32:
+                raise ValueError("device_conditions needs 1 <= input_words <= 32")
+            if int(payload_words) < int(input_words) + 2:
+                raise ValueError("device_conditions needs payload_words >= "
+                                 "input_words + 2 (inputs, ordinal, step)")
+            self.input_words = int(input_words)
+        elif any(s.when is not None for dg in dags for s in dg.steps):
+            raise ValueError("when needs device_conditions=True")
         self.step_policy = bool(step_policy)
         if self.step_policy and dynamic_capacity is None:
             raise ValueError("step_policy needs dynamic_capacity: the policy is "
@@ -495,8 +546,27 @@ class WorkflowPipeline:
                  stock.multiplier_q8], dtype=torch.int32).repeat(TC * 64).to(d)
             self.tmpl_timeout = torch.full((TC * 64,), int(self.timeout_cutoff),
                                            dtype=torch.int32, device=d)
+        if self.step_policy or self.device_conditions:
+            # one column serves both options
             self._run_tmpl_buf = torch.zeros(NR + 1, dtype=torch.int32, device=d)
             self.run_tmpl = self._run_tmpl_buf[:NR]
+        if self.device_conditions:
+            # see "conditions decided on the device". run_input and step_out
+            # have one spare row past the table, as run_tmpl has a spare word:
+            # admit() sends the rows of refused requests there.
+            IW = self.input_words
+            self._run_input_buf = torch.zeros((NR + 1) * IW, dtype=torch.int32, device=d)
+            self.run_input = self._run_input_buf[:NR * IW]
+            self._step_out_buf = torch.zeros((NR + 1) * 64, dtype=torch.int32, device=d)
+            self.step_out = self._step_out_buf[:NR * 64]
+            self.tmpl_cond = torch.zeros(TC * 64 * 4, dtype=torch.int32, device=d)
+            self.tmpl_cond_mask = torch.zeros(TC, dtype=torch.int64, device=d)
+            # 1 where the template's step is a CONDITION without a predicate:
+            # its output word is the admitted bit, written by admit()
+            self._tmpl_plain_cond = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+            self._bit_idx = torch.arange(64, dtype=torch.int64, device=d)
+            self._any_plain_cond = False
+            self.cond_counts = torch.zeros(2, dtype=torch.int64, device=d)
         for dag in templates:
             self.add_template(dag)
         self._capture_dynamic()
@@ -524,6 +594,81 @@ class WorkflowPipeline:
     # A FREE row can therefore hold a DISPATCHED step whose longer timeout
     # has not run out; wf_settle skips FREE rows.
     _POLICY_KINDS = (WFK_WORKER, WFK_FOR_EACH)
+
+    # ---- conditions decided on the device (dynamic mode, device_conditions) --
+    # Tables, allocated only with the option on:
+    #   run_input      [(NR+1)*IW]  the run's input words, written by admit()
+    #   step_out       [(NR+1)*64]  one output word per step: a WORKER or
+    #                  FOR_EACH step's is the wraparound sum of the result
+    #                  words of its children that finally succeeded, a
+    #                  CONDITION step's 1 or 0, everything else 0
+    #   run_tmpl       [NR]         shared with step_policy
+    #   tmpl_cond      [TC*64*4]    one record (code, a, b, imm) per step
+    #   tmpl_cond_mask [TC]         bit s = step s carries a predicate
+    #   cond_counts    [2]          predicates evaluated true / false
+    # Record: code bits 0..3 op (WFC_*), bit 4 negate, bits 8..9 lhs kind
+    # (1 INPUT, 2 OUT), bits 12..13 rhs kind (0 IMM, 1 INPUT, 2 OUT); a / b the
+    # operand index, imm the immediate. Signed 32-bit comparisons.
+    #
+    # wf_child_payload makes a child's payload (input words, ordinal, step,
+    # zeros), so its echo checksum depends on nothing else; wf_apply_out adds
+    # the checksum of each child counted done into its step's output word.
+    # wf_cond_eval, directly before the sweep, evaluates every PENDING step
+    # with a predicate whose deps are satisfied. An OUT operand must name a
+    # step among the transitive deps, so it is final when read, and inputs
+    # never change: a step that returns to PENDING evaluates the same again.
+    # A CONDITION without a predicate keeps its admitted bit, and admit()
+    # writes that bit as its output word.
+    _OUT_KINDS = (WFK_WORKER, WFK_FOR_EACH, WFK_CONDITION)
+
+    def _cond_record(self, dag: DagSpec, s: int) -> List[int]:
+        """Validated (code, a, b, imm) of step s's predicate."""
+        w = dag.steps[s].when
+        op = _WFC_OPS.get(w.op, w.op) if isinstance(w.op, str) else w.op
+        if isinstance(op, bool) or not isinstance(op, int) or not WFC_EQ <= op <= WFC_TRUTHY:
+            raise ValueError(f"unknown predicate op {w.op!r}")
+        reach, stack = set(), list(dag.steps[s].deps)
+        while stack:
+            j = stack.pop()
+            if 0 <= j < len(dag.steps) and j not in reach:
+                reach.add(j)
+                stack.extend(dag.steps[j].deps)
+
+        def operand(x, side):
+            if isinstance(x, int) and not isinstance(x, bool):
+                if side == "lhs":
+                    raise ValueError("the lhs of a predicate is ('input', k) or ('out', j)")
+                if not _I32_MIN <= x <= _I32_MAX:
+                    raise ValueError(f"immediate {x} is outside int32")
+                return 0, 0, x
+            if not (isinstance(x, (tuple, list)) and len(x) == 2
+                    and x[0] in ("input", "out") and isinstance(x[1], int)
+                    and not isinstance(x[1], bool)):
+                raise ValueError(f"bad predicate operand {x!r}")
+            if x[0] == "input":
+                if not 0 <= x[1] < self.input_words:
+                    raise ValueError(f"input word {x[1]} outside 0..{self.input_words - 1}")
+                return 1, x[1], 0
+            if x[1] not in reach:
+                raise ValueError(
+                    f"step {s} reads the output of step {x[1]}, which is not among its "
+                    "(transitive) dependencies: an operand must be final when read")
+            if dag.steps[x[1]].kind not in self._OUT_KINDS:
+                raise ValueError(f"step {x[1]} has no output (WORKER, FOR_EACH and "
+                                 "CONDITION steps have one)")
+            return 2, x[1], 0
+
+        lk, a, _ = operand(w.lhs, "lhs")
+        rk, b, imm = (0, 0, 0) if op == WFC_TRUTHY else operand(w.rhs, "rhs")
+        return [op | (16 if w.negate else 0) | (lk << 8) | (rk << 12), a, b, imm]
+
+    def cond_stats(self) -> dict:
+        """Cumulative predicates evaluated true / false."""
+        self._require_dynamic(True, "cond_stats")
+        if not self.device_conditions:
+            raise RuntimeError("cond_stats needs device_conditions=True")
+        c = self.cond_counts.cpu().tolist()
+        return {"true": c[0], "false": c[1]}
 
     def _check_policy(self, spec: StepSpec) -> None:
         if spec.retry is None and not spec.timeout_ticks:
@@ -574,6 +719,10 @@ class WorkflowPipeline:
                     raise ValueError("ttl_ticks is a positive tick count on an "
                                      "APPROVAL step")
             self._check_policy(spec)
+            if spec.when is not None and not self.device_conditions:
+                raise ValueError("when needs device_conditions=True")
+        cond_recs = {s: self._cond_record(dag, s) for s, sp in enumerate(dag.steps)
+                     if sp.when is not None}
         deps = torch.zeros(64, dtype=torch.int64)
         kinds = torch.zeros(64, dtype=torch.uint8)
         todo = torch.zeros(64, dtype=torch.int32)
@@ -620,13 +769,27 @@ class WorkflowPipeline:
             self.tmpl_policy[t * 256:t * 256 + 256].copy_(
                 torch.tensor(pol, dtype=torch.int32))
             self.tmpl_timeout[row].copy_(torch.tensor(tmo, dtype=torch.int32))
+        if self.device_conditions:
+            rec, cm = [0] * 256, 0
+            for s, r4 in cond_recs.items():
+                rec[4 * s:4 * s + 4] = r4
+                cm |= 1 << s
+            self.tmpl_cond[t * 256:t * 256 + 256].copy_(
+                torch.tensor(rec, dtype=torch.int32))
+            self.tmpl_cond_mask[t:t + 1].fill_(cm - (1 << 64) if cm >= (1 << 63) else cm)
+            plain = [int(s < len(dag.steps) and dag.steps[s].kind == WFK_CONDITION
+                         and dag.steps[s].when is None) for s in range(64)]
+            self._tmpl_plain_cond[row].copy_(torch.tensor(plain, dtype=torch.int32))
+            self._any_plain_cond = self._any_plain_cond or any(plain)
         self._tmpl_cond.append(cbits - (1 << 64) if cbits >= (1 << 63) else cbits)
         self.n_templates = t + 1
         return t
 
-    def admit(self, templates: Sequence[int], cond_bits=None, fanout=None):
+    def admit(self, templates: Sequence[int], cond_bits=None, fanout=None, inputs=None):
         """Admit one run per template id into the lowest FREE slots; returns
-        (slots, gens). slots[i] == -1: the table was full for request i."""
+        (slots, gens). slots[i] == -1: the table was full for request i.
+        `inputs[i]` (device_conditions) holds at most input_words ints in
+        int32 range, zero padded: the run's input words."""
         self._require_dynamic(True, "admit")
         tl = [int(t) for t in templates]
         n = len(tl)
@@ -645,17 +808,35 @@ class WorkflowPipeline:
                   for c in cond_bits]
         if len(fl) != n or len(cl) != n:
             raise ValueError("cond_bits / fanout must match templates in length")
+        IW = self.input_words if self.device_conditions else 0
+        if inputs is not None and not self.device_conditions:
+            raise ValueError("inputs need device_conditions=True")
+        il: List[int] = []
+        if IW:
+            rows = [()] * n if inputs is None else [tuple(r) for r in inputs]
+            if len(rows) != n:
+                raise ValueError("inputs must match templates in length")
+            for r in rows:
+                if len(r) > IW:
+                    raise ValueError(f"a run has at most {IW} input words")
+                for v in r:
+                    if isinstance(v, bool) or not isinstance(v, int) \
+                            or not _I32_MIN <= v <= _I32_MAX:
+                        raise ValueError(f"input word {v!r} is not an int32")
+                il += list(r) + [0] * (IW - len(r))
         if n == 0:
             return [], []
-        # one H2D: [cond as int64 | template ids | fanouts] in one buffer
-        req = torch.empty(4 * n, dtype=torch.int32)
+        # one H2D: [cond as int64 | template ids | fanouts | inputs] in one buffer
+        req = torch.empty(4 * n + n * IW, dtype=torch.int32)
+        if IW:
+            req[4 * n:] = torch.tensor(il, dtype=torch.int32)
         req[:2 * n].view(torch.int64).copy_(torch.tensor(cl, dtype=torch.int64))
         req[2 * n:3 * n] = torch.tensor(tl, dtype=torch.int32)
-        req[3 * n:] = torch.tensor(fl, dtype=torch.int32)
+        req[3 * n:4 * n] = torch.tensor(fl, dtype=torch.int32)
         req = req.to(self.device)
         out = torch.empty(2 * n, dtype=torch.int32, device=self.device)
         self.ext.wf_admit(
-            req[2 * n:3 * n], req[:2 * n].view(torch.int64), req[3 * n:],
+            req[2 * n:3 * n], req[:2 * n].view(torch.int64), req[3 * n:4 * n],
             self.tmpl_deps, self.tmpl_kind, self.tmpl_todo, self.tmpl_maxp,
             self.tmpl_delay, self.tmpl_nsteps,
             self.step_state, self.step_attempts, self.deps_mask, self.step_kind,
@@ -665,12 +846,26 @@ class WorkflowPipeline:
             self.run_state, self.run_active, self.run_life, self.run_gen,
             self.tick_buf, self._free_mask, self._blk_scan,
             out[:n], out[n:], self.admit_count)
-        if self.step_policy:
+        if self.step_policy or self.device_conditions:
             # run_tmpl is a run column wf_admit does not know: one indexed
             # store of the accepted requests' template ids. A refused request
             # has slot -1, and -1 mod (NR + 1) = NR is the spare word past the
             # table, so no mask and no host round trip is needed.
-            self._run_tmpl_buf[torch.remainder(out[:n], self.NR + 1)] = req[2 * n:3 * n]
+            dst = torch.remainder(out[:n], self.NR + 1)
+            self._run_tmpl_buf[dst] = req[2 * n:3 * n]
+        if self.device_conditions:
+            # the same trick for the run's input row and its output row. The
+            # outputs start at zero, but for a CONDITION step without a
+            # predicate: its output is the bit it was admitted with.
+            dst = dst.long()
+            self._run_input_buf.view(-1, IW)[dst] = req[4 * n:].view(n, IW)
+            if self._any_plain_cond:
+                bits = (req[:2 * n].view(torch.int64)[:, None] >> self._bit_idx[None, :]) & 1
+                self._step_out_buf.view(-1, 64)[dst] = \
+                    bits.to(torch.int32) \
+                    * self._tmpl_plain_cond.view(-1, 64)[req[2 * n:3 * n].long()]
+            else:       # no template has such a step: fewer launches per admit
+                self._step_out_buf.view(-1, 64)[dst] = 0
         if self.external and self._any_ttl:
             # hold_ttl is a run column like max_parallel: the template's row
             # goes into every slot just filled (all zero until a template
@@ -898,6 +1093,8 @@ class WorkflowPipeline:
             counters.append(self.ev_count)
         if self.external:
             counters += [self.hold_counts, self.hold_open]
+        if self.device_conditions:
+            counters.append(self.cond_counts)
         saved = [(t, t.clone()) for t in counters]
         for _ in range(2):
             self._tick_device_body()
@@ -987,6 +1184,14 @@ class WorkflowPipeline:
         ext = self.ext
         cap, world, Wd = self.pad_cap, self.world, self.W
         self.tick_buf += 1
+        if self.device_conditions:
+            # predicates first: condition bits for the sweep to commit, and
+            # false guards -> SKIPPED (see "conditions decided on the device")
+            ext.wf_cond_eval(self.step_state, self.deps_mask, self.step_kind,
+                             self.run_life, self.run_active, self.run_tmpl,
+                             self.tmpl_cond, self.tmpl_cond_mask, self.run_input,
+                             self.step_out, self.cond_bits, self.cond_counts,
+                             self.input_words)
         # sweep: readiness -> dispatch list + fresh approval holds
         self.disp_count.zero_()
         self.appr_count.zero_()
@@ -1013,6 +1218,12 @@ class WorkflowPipeline:
                       self.child_count, self.children_emitted,
                       self.dispatch_tick, self.tick_buf,
                       self.order_buf, self.valid_buf)
+        if self.device_conditions:
+            # a child's payload is (run input, ordinal, step): its result is
+            # then a function of those alone
+            ext.wf_child_payload(self.child_tag, self.child_seq, self.child_count,
+                                 self.run_input, self.child_payload,
+                                 self.input_words, Wd)
 
         # K2 load view + routing order refresh
         ext.worker_precompute_into(self.w_pool, self.w_active, self.w_maxp,
@@ -1066,10 +1277,17 @@ class WorkflowPipeline:
         self._exchange_back()
 
         # owner-rank application + aggregation + roll-up
-        ext.wf_apply(self.pad_send_slots, self.pad_send_cnt, self.child_tag,
-                     self.child_seq, self.rq_prev_tag, self.rq_prev_seq,
-                     self.children_done, self.children_fail,
-                     self.children_out, self.fail_ppt, self.drop_ppt, cap, world)
+        if self.device_conditions:
+            ext.wf_apply_out(self.pad_send_slots, self.pad_send_cnt, self.child_tag,
+                             self.child_seq, self.rq_prev_tag, self.rq_prev_seq,
+                             self.children_done, self.children_fail,
+                             self.children_out, self.pad_sums_back, self.step_out,
+                             self.fail_ppt, self.drop_ppt, cap, world)
+        else:
+            ext.wf_apply(self.pad_send_slots, self.pad_send_cnt, self.child_tag,
+                         self.child_seq, self.rq_prev_tag, self.rq_prev_seq,
+                         self.children_done, self.children_fail,
+                         self.children_out, self.fail_ppt, self.drop_ppt, cap, world)
         ext.wf_apply_dead(self.dead_src, self.dead_count, self.child_tag,
                           self.rq_prev_tag, self.children_fail, self.children_out)
         # K4-WF: steps whose children were lost (worker crash) time out and

@@ -23,17 +23,28 @@ On a pipeline with `step_policy=True` registration also lowers each worker
 step's `retry` block and `timeout_sec` (`lower_retry`, `dag_from_workflow`):
 a step retries as often, and waits as many ticks, as the host engine would.
 
-Wiring an API route to this table, and result / output materialisation, are
-not done here.
+On a pipeline with `device_conditions=True` registration lowers `condition`
+steps and `condition` guards over the run's input and over step outputs
+(`lower_condition`), `submit(input=...)` maps the run's input fields onto the
+device's input words, and `step_outputs()` reads a run's output words. A step
+whose guard is false shows as PENDING -> SKIPPED in the events, which
+`timeline_of` reports as `step_condition_evaluated {"value": False}` with
+status succeeded; the host engine completes such a step as succeeded without
+recording an event. That is the one difference.
+
+Wiring an API route to this table, and materialising job results (a step's
+output word is a checksum, not the job's result document), are not done here.
 """
 from __future__ import annotations
 
 import math
+import re
 from collections import deque
 from typing import Any, Deque, Dict, List, NamedTuple, Optional, Tuple, Union
 
 from ..ops.reference import wf_backoff_ref
 from ..ops.wf_pipeline import (
+    CondSpec,
     DagSpec,
     RetrySpec,
     StepSpec,
@@ -185,16 +196,106 @@ def lower_retry(step: Step, tick_seconds: float) -> Optional[RetrySpec]:
     return spec
 
 
+_OPS = ["==", "!=", ">=", "<=", ">", "<"]         # eval.py's order of search
+_FLIP = {"==": "==", "!=": "!=", ">": "<", "<": ">", ">=": "<=", "<=": ">="}
+_RE_INPUT = re.compile(r"input\.([A-Za-z_][A-Za-z0-9_]*)\Z")
+_RE_STEP = re.compile(r"steps\.([A-Za-z0-9_-]+)\.output\Z")
+_RE_INT = re.compile(r"[+-]?[0-9]+\Z")
+
+
+def lower_condition(expr: str, steps: List[Step], i: int, names: List[str],
+                    input_words: int) -> Optional[CondSpec]:
+    """The device predicate of step i's `condition` expression, or None if the
+    device would not decide it as `eval.eval_condition` does. The subset is
+    `[!] lhs [op rhs]` with op one of == != >= <= > <, split exactly as
+    eval.py splits it. An operand is `input.<name>` (an int field of the
+    run's input; names take word indices in `names`, in order of first
+    appearance), `steps.<id>.output` of a step among the transitive
+    dependencies that is an unguarded, non-for_each worker (a number) or a
+    condition step (a boolean), an integer literal in int32 range, or `true` /
+    `false`. Numbers compare with numbers, with any op; booleans with
+    booleans, with == and != only (the host compares everything else as
+    strings, or says False). A literal on the left is flipped to the right; a
+    bare operand is its truthiness."""
+    index = {st.id: j for j, st in enumerate(steps)}
+    reach, stack = set(), list(steps[i].depends_on)
+    while stack:
+        j = index.get(stack.pop())
+        if j is not None and j not in reach:
+            reach.add(j)
+            stack.extend(steps[j].depends_on)
+    text = expr.strip()
+    negate = text.startswith("!")
+    if negate:
+        text = text[1:].strip()
+    if not text or text.startswith("!"):
+        return None
+    added: List[str] = []
+
+    def operand(tok: str):
+        """(class, operand): class "num" or "bool", literal flag."""
+        tok = tok.strip()
+        m = _RE_INPUT.match(tok)
+        if m:
+            name = m.group(1)
+            known = names + added
+            if name not in known:
+                if len(known) >= input_words:
+                    return None
+                added.append(name)
+                known = names + added
+            return "num", ("input", known.index(name)), False
+        m = _RE_STEP.match(tok)
+        if m:
+            j = index.get(m.group(1))
+            if j is None or j not in reach:
+                return None
+            ref = steps[j]
+            if ref.type == "condition":
+                return "bool", ("out", j), False
+            if ref.type == "worker" and not ref.for_each and not ref.condition:
+                return "num", ("out", j), False
+            return None
+        if tok in ("true", "false"):
+            return "bool", int(tok == "true"), True
+        if _RE_INT.match(tok):
+            v = int(tok)
+            return ("num", v, True) if -(1 << 31) <= v < (1 << 31) else None
+        return None
+
+    op = next((o for o in _OPS if o in text), None)
+    if op is None:
+        a = operand(text)
+        if a is None or a[2]:
+            return None
+        spec = CondSpec("truthy", a[1], 0, negate)
+    else:
+        k = text.find(op)
+        a, b = operand(text[:k]), operand(text[k + len(op):])
+        if a is None or b is None or a[0] != b[0] or (a[2] and b[2]):
+            return None
+        if a[0] == "bool" and op not in ("==", "!="):
+            return None
+        if a[2]:
+            a, b, op = b, a, _FLIP[op]
+        spec = CondSpec(op, a[1], b[1], negate)
+    names.extend(added)
+    return spec
+
+
 def dag_from_workflow(workflow: Any, items_len: int,
                       tick_seconds: float = 1.0,
                       approval_ttl_sec: float = 0.0,
                       step_policy: bool = False,
-                      timeout_cutoff: int = 8) -> Optional[DagSpec]:
+                      timeout_cutoff: int = 8,
+                      conditions: bool = False,
+                      input_words: int = 8) -> Optional[DagSpec]:
     """Lower a workflow (a `Workflow`, or its `{"steps": {id: step}}` dict
     form) to a device `DagSpec`; steps are indexed in `workflow.steps` order.
     Returns None when the workflow cannot run on the device, and the caller
     stays on the host engine: more than 64 steps, a step type other than
-    worker / approval / delay, a `condition` expression, `delay_until`,
+    worker / approval / delay (or `condition`, with `conditions`), a
+    `condition` expression without `conditions`, `delay_until`,
     `on_error`, a dependency on a later or unknown step, or a `for_each` over
     no items (the device cannot complete a step with nothing to emit).
     `approval_ttl_sec` > 0 gives every approval step that expiry, rounded up
@@ -212,7 +313,13 @@ def dag_from_workflow(workflow: Any, items_len: int,
     to `timeout_cutoff`, the pipeline's floor. On the device a step's timeout
     is how long results that never came are waited for before the retry; the
     host engine hands it to the job as its deadline. `retry` and `timeout_sec`
-    on approval and delay steps mean nothing to either engine."""
+    on approval and delay steps mean nothing to either engine.
+
+    With `conditions` (a pipeline with device_conditions=True) a `condition`
+    step lowers to a CONDITION step with a predicate and a `condition` on a
+    worker, for_each, approval or delay step to a guard (see
+    `lower_condition`; an expression outside its subset returns None). The
+    result's `input_names` lists the input fields in word order."""
     steps = _steps_of(workflow)
     ttl = max(0, int(math.ceil(approval_ttl_sec / tick_seconds)))
     if len(steps) > 64:
@@ -221,8 +328,11 @@ def dag_from_workflow(workflow: Any, items_len: int,
     if len(index) != len(steps):
         return None
     specs: List[StepSpec] = []
+    names: List[str] = []
     for i, st in enumerate(steps):
-        if st.condition or st.delay_until or st.on_error:
+        if st.delay_until or st.on_error:
+            return None
+        if (st.condition or st.type == "condition") and not conditions:
             return None
         if st.retry is not None and not step_policy:
             return None
@@ -232,6 +342,17 @@ def dag_from_workflow(workflow: Any, items_len: int,
             if j is None or j >= i:
                 return None
             deps.append(j)
+        when = None
+        cond = (st.condition or "").strip()
+        if not cond and (st.type == "condition" or st.condition):
+            return None              # the host fails, or never runs, such a step
+        if cond:
+            when = lower_condition(cond, steps, i, names, int(input_words))
+            if when is None:
+                return None
+        if st.type == "condition":
+            specs.append(StepSpec(WFK_CONDITION, deps=deps, when=when))
+            continue
         if st.type == "worker":
             policy = {}
             if step_policy:
@@ -249,17 +370,19 @@ def dag_from_workflow(workflow: Any, items_len: int,
                 if items_len <= 0:
                     return None
                 specs.append(StepSpec(WFK_FOR_EACH, deps=deps, fanout=int(items_len),
-                                      max_parallel=int(st.max_parallel), **policy))
+                                      max_parallel=int(st.max_parallel), when=when,
+                                      **policy))
             else:
-                specs.append(StepSpec(WFK_WORKER, deps=deps, **policy))
+                specs.append(StepSpec(WFK_WORKER, deps=deps, when=when, **policy))
         elif st.type == "approval":
-            specs.append(StepSpec(WFK_APPROVAL, deps=deps, ttl_ticks=ttl))
+            specs.append(StepSpec(WFK_APPROVAL, deps=deps, ttl_ticks=ttl, when=when))
         elif st.type == "delay":
             ticks = int(math.ceil(st.delay_sec / tick_seconds))
-            specs.append(StepSpec(WFK_DELAY, deps=deps, delay_ticks=max(0, ticks)))
+            specs.append(StepSpec(WFK_DELAY, deps=deps, delay_ticks=max(0, ticks),
+                                  when=when))
         else:
             return None
-    return DagSpec(steps=specs)
+    return DagSpec(steps=specs, input_names=names)
 
 
 class DeviceRunTable:
@@ -279,7 +402,9 @@ class DeviceRunTable:
         self._tmpl_ttl: Dict[int, List[int]] = {}    # template id -> hold ttl per step
         self._handle: Dict[str, Tuple[int, int]] = {}
         self._run_of: Dict[Tuple[int, int], str] = {}
-        self._queue: Deque[Tuple[str, int, int, int]] = deque()
+        self._tmpl_inputs: Dict[int, List[str]] = {}  # template id -> input field names
+        # (run id, template, cond bits, fanout, input words)
+        self._queue: Deque[Tuple[str, int, int, int, Tuple[int, ...]]] = deque()
         self._queued_ids: set = set()     # run ids in _queue
         self._reported: List[Tuple[str, str]] = []  # queued runs cancelled
 
@@ -298,9 +423,12 @@ class DeviceRunTable:
     def _admit(self, reqs) -> int:
         """Admit the requests in order; returns how many got a slot (the
         device accepts a prefix)."""
+        extra = {}
+        if getattr(self.pipe, "device_conditions", False):
+            extra["inputs"] = [r[4] for r in reqs]
         slots, gens = self.pipe.admit([r[1] for r in reqs],
                                       cond_bits=[r[2] for r in reqs],
-                                      fanout=[r[3] for r in reqs])
+                                      fanout=[r[3] for r in reqs], **extra)
         n = 0
         for r, slot, gen in zip(reqs, slots, gens):
             if slot < 0:
@@ -318,14 +446,18 @@ class DeviceRunTable:
         to submit() runs of it with, or None if the workflow must stay on the
         host engine. Events of such runs carry the workflow's step ids. On a
         pipeline with step_policy the steps' `retry` blocks and `timeout_sec`
-        are lowered too (see `dag_from_workflow`)."""
+        are lowered too, on one with device_conditions the `condition`
+        expressions (see `dag_from_workflow`)."""
         dag = dag_from_workflow(
             workflow, items_len, tick_seconds, approval_ttl_sec,
             step_policy=bool(getattr(self.pipe, "step_policy", False)),
-            timeout_cutoff=int(getattr(self.pipe, "timeout_cutoff", 8)))
+            timeout_cutoff=int(getattr(self.pipe, "timeout_cutoff", 8)),
+            conditions=bool(getattr(self.pipe, "device_conditions", False)),
+            input_words=int(getattr(self.pipe, "input_words", 8)))
         if dag is None:
             return None
         t = self.pipe.add_template(dag)
+        self._tmpl_inputs[t] = list(dag.input_names)
         wf_id = getattr(workflow, "id", None)
         if wf_id is None and isinstance(workflow, dict):
             wf_id = workflow.get("id", "")
@@ -341,17 +473,34 @@ class DeviceRunTable:
             info = self._tmpl_info[template_id] = ("", None, row.cpu().tolist()[:n])
         return info
 
+    def _input_words(self, template_id: int, input: Optional[Dict[str, Any]]):
+        """The run's input dict as the template's input words."""
+        words = []
+        for name in self._tmpl_inputs.get(template_id, ()):
+            v = (input or {}).get(name)
+            if isinstance(v, bool) or not isinstance(v, int) \
+                    or not -(1 << 31) <= v < (1 << 31):
+                raise ValueError(f"input field {name!r} must be an int in int32 "
+                                 f"range for the device to decide on it, got {v!r}")
+            words.append(v)
+        return tuple(words)
+
     def submit(self, run_id: str, template_id: int, cond_bits: int = 0,
-               fanout: int = 0) -> bool:
+               fanout: int = 0, input: Optional[Dict[str, Any]] = None) -> bool:
         """Start a run. Returns True if it was admitted now, False if the
-        table was full and it waits (FIFO) for the next poll()."""
+        table was full and it waits (FIFO) for the next poll(). `input` is the
+        run's input: the fields the template's conditions name go to the
+        device as input words. A named field that is missing, not an int, a
+        bool or outside int32 raises ValueError; such a run stays on the host
+        engine."""
         if self._known(run_id):
             raise ValueError(f"run {run_id!r} is already live or queued")
         if not 0 <= int(template_id) < self.pipe.n_templates:
             raise ValueError(f"unregistered template id {template_id}")
         if not 0 <= int(fanout) <= self.pipe.CB:
             raise ValueError(f"fanout {fanout} can never be emitted")
-        req = (run_id, int(template_id), int(cond_bits), int(fanout))
+        req = (run_id, int(template_id), int(cond_bits), int(fanout),
+               self._input_words(int(template_id), input))
         # nobody overtakes a waiting submission
         if not self._queue and self._admit([req]) == 1:
             return True
@@ -505,6 +654,20 @@ class DeviceRunTable:
         _, ids, kinds = self._info(self._tmpl_of[run_id])
         row = self.pipe.step_state[h[0] * 64:h[0] * 64 + len(kinds)].cpu().tolist()
         return {(ids[s] if ids else s): _STEP_STATUS[v] for s, v in enumerate(row)}
+
+    def step_outputs(self, run_id: str) -> Dict[Union[str, int], int]:
+        """The output word of every step of an admitted run, by step id (by
+        step index for a template added without register()): a worker or
+        for_each step's is the wraparound sum of its succeeded children's
+        result words, a condition step's 1 or 0, anything else 0."""
+        if not getattr(self.pipe, "device_conditions", False):
+            raise RuntimeError("step_outputs needs a pipeline with device_conditions")
+        h = self._handle.get(run_id)
+        if h is None:
+            raise KeyError(run_id)
+        _, ids, kinds = self._info(self._tmpl_of[run_id])
+        row = self.pipe.step_out[h[0] * 64:h[0] * 64 + len(kinds)].cpu().tolist()
+        return {(ids[s] if ids else s): v for s, v in enumerate(row)}
 
     def poll(self) -> List[Tuple[str, str]]:
         """Drain the device's step events (journal on), then its completion

@@ -47,10 +47,23 @@ that a kernel trace of the run holds the pair's kernels from the dynamic
 window only; --settle-pass ROWS runs nothing but the quiet pass timings at
 that size, for a kernel trace of one table size.
 
+With --conditions nothing but this runs: the churn of a branching template,
+`a: worker -> c: condition(a's output > K) -> w: worker if true, f: for_each
+if false`, on a pipeline with device_conditions=True, where wf_cond_eval
+decides c and the two guards from the output word of a; against the same work
+with the predicate evaluated before admission and the option off: one
+template per outcome (`a -> c -> w` with c's bit set, `a -> c -> f` with it
+clear), the host choosing by the same rule. Inputs alternate between 2K and 0,
+so half of the runs take each branch. The two windows alternate; it reports
+runs/s of both, the ratio, and the predicate counters. --cond-pass ROWS runs
+nothing but the quiet passes of wf_cond_eval (nothing PENDING) and wf_settle
+(nothing DISPATCHED) alone, alternating, at that size.
+
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --events
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --approvals
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --step-policy
+    python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --conditions
 """
 import argparse
 import json
@@ -92,6 +105,11 @@ def main() -> int:
                     help="leave the static readmit baseline out (kernel traces)")
     ap.add_argument("--settle-pass", type=int, default=0, metavar="ROWS",
                     help="only time the quiet settle pass and the pair at ROWS rows")
+    ap.add_argument("--conditions", action="store_true",
+                    help="only the branching churn: conditions decided on the device "
+                         "against the predicate evaluated before admission")
+    ap.add_argument("--cond-pass", type=int, default=0, metavar="ROWS",
+                    help="only time the quiet wf_cond_eval and wf_settle passes at ROWS rows")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="rehearse the host logic on the reference backend (no timings)")
     args = ap.parse_args()
@@ -194,6 +212,154 @@ def main() -> int:
         print(json.dumps({"metric": "settle pass vs timeout scan + commit, alone",
                           "unit": "us", "timed": bool(use_gpu),
                           "pass_times": [settle_pass_times(ext, args.settle_pass, False)]}))
+        return 0
+
+    def cond_pass_times(ext, NR, reps=15):
+        """The quiet passes of wf_cond_eval and wf_settle alone on one all-LIVE
+        table of NR rows, alternating, one device-event pair per side and
+        round; µs, median (min..max). Every step of the one template carries
+        a predicate, and no step is PENDING (or DISPATCHED): both passes read
+        their columns and write nothing."""
+        d = device
+        st = torch.full((NR * 64,), WFS_SUCCEEDED, dtype=torch.uint8, device=d)
+
+        def zi(n=NR * 64):
+            return torch.zeros(n, dtype=torch.int32, device=d)
+
+        att, todo, out, fail, maxp, nready, dtick, sout = (zi() for _ in range(8))
+        tickb = torch.tensor([5], dtype=torch.int32, device=d)
+        ones8 = torch.ones(NR, dtype=torch.uint8, device=d)
+        rtmpl = zi(NR)
+        policy = torch.tensor([2, 2, 16, 512], dtype=torch.int32).repeat(64).to(d)
+        timeout = torch.full((64,), 8, dtype=torch.int32, device=d)
+        tcount = torch.zeros(1, dtype=torch.int64, device=d)
+        rcount = torch.zeros(1, dtype=torch.int64, device=d)
+        deps = torch.zeros(NR * 64, dtype=torch.int64, device=d)
+        kind = torch.zeros(NR * 64, dtype=torch.uint8, device=d)
+        crec = torch.tensor([7 | 1 << 8, 0, 0, 0], dtype=torch.int32).repeat(64).to(d)
+        cmask = torch.full((1,), -1, dtype=torch.int64, device=d)
+        rin = zi(NR * 8)
+        cbits = torch.zeros(NR, dtype=torch.int64, device=d)
+        ccount = torch.zeros(2, dtype=torch.int64, device=d)
+
+        def settle():
+            ext.wf_settle(st, att, todo, out, fail, maxp, nready, dtick, ones8, rtmpl,
+                          policy, timeout, tickb, tcount, rcount)
+
+        def cond():
+            ext.wf_cond_eval(st, deps, kind, ones8, ones8, rtmpl, crec, cmask, rin,
+                             sout, cbits, ccount, 8)
+
+        settle_t, cond_t = Timer(), Timer()
+        for i in range(reps + 3):
+            settle_t(settle)
+            cond_t(cond)
+            sync()
+            if i < 3:                              # warm-up launches
+                settle_t.take_ms(), cond_t.take_ms()
+        assert int(ccount.cpu().sum()) == 0 and int(tcount.cpu()[0]) == 0
+        if not use_gpu:
+            return None
+        return {"rows": NR, "case": "quiet",
+                "settle_us": spread([1000 * x for x in settle_t.take_ms()]),
+                "cond_eval_us": spread([1000 * x for x in cond_t.take_ms()])}
+
+    if args.cond_pass:
+        from cordum_amd.ops import get_ext
+        from cordum_amd.ops.pipeline import _RefOps
+
+        ext = get_ext(required=True) if use_gpu else _RefOps()
+        print(json.dumps({"metric": "quiet wf_cond_eval pass vs quiet wf_settle pass, alone",
+                          "unit": "us", "timed": bool(use_gpu),
+                          "pass_times": [cond_pass_times(ext, args.cond_pass)]}))
+        return 0
+
+    if args.conditions:
+        from cordum_amd.ops.wf_pipeline import (
+            CondSpec, StepSpec, WFK_CONDITION, WFK_FOR_EACH, WFK_WORKER)
+
+        K = 1000
+        branching = DagSpec(steps=[
+            StepSpec(WFK_WORKER),
+            StepSpec(WFK_CONDITION, deps=[0], when=CondSpec(">", ("out", 0), K)),
+            StepSpec(WFK_WORKER, deps=[1], when=CondSpec("truthy", ("out", 1))),
+            StepSpec(WFK_FOR_EACH, deps=[1], fanout=args.fanout,
+                     when=CondSpec("==", ("out", 1), 0)),
+        ])
+        decided = [
+            DagSpec(steps=[StepSpec(WFK_WORKER), StepSpec(WFK_CONDITION, deps=[0], cond=True),
+                           StepSpec(WFK_WORKER, deps=[1])]),
+            DagSpec(steps=[StepSpec(WFK_WORKER), StepSpec(WFK_CONDITION, deps=[0], cond=False),
+                           StepSpec(WFK_FOR_EACH, deps=[1], fanout=args.fanout)]),
+        ]
+        words = max(10, args.payload_bytes // 4)
+        kw = dict(common, payload_words=words)
+        on = WorkflowPipeline(dags=[branching], dynamic_capacity=args.runs,
+                              device_conditions=True, **kw)
+        off = WorkflowPipeline(dags=decided, dynamic_capacity=args.runs, **kw)
+
+        def window_of(pipe, admit):
+            state = {"live": 0, "n": 0}
+
+            def fill():
+                want = args.runs - state["live"]
+                if want:
+                    # request i of the pipeline's life: input 2K (true) or 0 (false)
+                    big = [(state["n"] + i) % 2 == 0 for i in range(want)]
+                    got = admit(pipe, big)
+                    k = sum(1 for s in got if s >= 0)
+                    state["live"] += k
+                    state["n"] += k
+            fill()
+            assert state["live"] == args.runs
+
+            def window(n_ticks):
+                ok = 0
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(n_ticks):
+                    pipe.tick()
+                    _, _, states = pipe.drain_completed()
+                    ok += sum(1 for s in states if s == WFS_SUCCEEDED)
+                    state["live"] -= len(states)
+                    fill()
+                sync()
+                return ok, time.perf_counter() - t0
+            return window
+
+        modes = [
+            ("conditions", window_of(on, lambda p, big: p.admit(
+                [0] * len(big), inputs=[[2 * K if b else 0] for b in big])[0])),
+            ("preevaluated", window_of(off, lambda p, big: p.admit(
+                [0 if b else 1 for b in big])[0])),
+        ]
+        for _, window in modes:
+            window(args.warmup)
+        rate = {name: [] for name, _ in modes}
+        tick_ms = {name: [] for name, _ in modes}
+        for _ in range(args.repeats):
+            for name, window in modes:
+                ok, dt = window(args.ticks)
+                rate[name].append(ok / dt)
+                tick_ms[name].append(dt / args.ticks * 1000.0)
+        print(json.dumps({
+            "metric": "sustained workflow runs/s, conditions decided on the device vs "
+                      "evaluated before admission (worker -> condition -> worker | "
+                      "1->%d for_each)" % args.fanout,
+            "unit": "runs/s", "timed": bool(use_gpu),
+            "runs": args.runs, "fanout": args.fanout, "workers": args.workers,
+            "payload_words": words, "ticks_per_window": args.ticks, "repeats": args.repeats,
+            "conditions_runs_per_s": spread(rate["conditions"]),
+            "preevaluated_runs_per_s": spread(rate["preevaluated"]),
+            "conditions_over_preevaluated": round(
+                statistics.median(rate["conditions"])
+                / max(1e-9, statistics.median(rate["preevaluated"])), 3),
+            "ratio_per_repeat": [round(a / max(1e-9, b), 3) for a, b in
+                                 zip(rate["conditions"], rate["preevaluated"])],
+            "ms_per_tick": {k: spread(v) for k, v in tick_ms.items()},
+            "cond_stats": on.cond_stats(),
+            "graph": {"conditions": bool(on._wf_graph), "preevaluated": bool(off._wf_graph)},
+        }))
         return 0
 
     # ---- dynamic mode ------------------------------------------------------
