@@ -309,16 +309,6 @@ class _RefOps:
                          rq_src, rq_widx, rq_attempts, rq_count, rq_dead,
                          dead_src, dead_count)
 
-    def wf_sweep(self, *a):
-        from .reference import wf_sweep_ref
-
-        wf_sweep_ref(*a)
-
-    def wf_expand(self, *a):
-        from .reference import wf_expand_ref
-
-        wf_expand_ref(*a)
-
     def wf_apply(self, ss, sc, ct, cs, rpt, rps, cd, cf, co, fail_ppt,
                  drop_ppt, cap, world):
         from .reference import wf_apply_ref
@@ -326,92 +316,25 @@ class _RefOps:
         wf_apply_ref(ss, sc, ct, cs, rpt, rps, cd, cf, co, int(fail_ppt),
                      int(drop_ppt), int(cap), int(world))
 
-    def wf_apply_dead(self, *a):
-        from .reference import wf_apply_dead_ref
-
-        wf_apply_dead_ref(*a)
-
     def wf_commit(self, st, sa, ctd, co, cd, cf, mp, nr, tick, max_retries, rc):
         from .reference import wf_commit_ref
 
         wf_commit_ref(st, sa, ctd, co, cd, cf, mp, nr, tick, int(max_retries), rc)
-
-    def wf_status(self, *a):
-        from .reference import wf_status_ref
-
-        wf_status_ref(*a)
-
-    def wf_grant(self, gr, gs, v, n, st):
-        from .reference import wf_grant_ref
-
-        wf_grant_ref(gr, gs, v, int(n), st)
 
     def wf_timeout_scan(self, st, co, cf, dt, tick, cutoff, tc):
         from .reference import wf_timeout_scan_ref
 
         wf_timeout_scan_ref(st, co, cf, dt, tick, int(cutoff), tc)
 
-    def wf_readmit(self, *a):
-        from .reference import wf_readmit_ref
-
-        args = list(a)
-        args[14] = int(args[14])  # filter_state
-        wf_readmit_ref(*args)
-
-    def wf_admit(self, *a):
-        from .reference import wf_admit_ref
-
-        wf_admit_ref(*a)
-
-    def wf_cancel(self, *a):
-        from .reference import wf_cancel_ref
-
-        wf_cancel_ref(*a)
-
     def wf_retire(self, rl, ra, rs, rg, ns, co, dt, tick, cutoff, ds, dg, dst, dc):
         from .reference import wf_retire_ref
 
         wf_retire_ref(rl, ra, rs, rg, ns, co, dt, tick, int(cutoff), ds, dg, dst, dc)
 
-    def wf_journal(self, st, rl, rg, tick, phase, shs, shg, rec, cnt):
-        from .reference import wf_journal_ref
-
-        wf_journal_ref(st, rl, rg, tick, int(phase), shs, shg, rec, cnt)
-
-    def wf_hold_scan(self, *a):
-        from .reference import wf_hold_scan_ref
-
-        wf_hold_scan_ref(*a)
-
-    def wf_settle(self, *a):
-        from .reference import wf_settle_ref
-
-        wf_settle_ref(*a)
-
-    def wf_cond_eval(self, *a):
-        from .reference import wf_cond_eval_ref
-
-        wf_cond_eval_ref(*a)
-
-    def wf_child_payload(self, *a):
-        from .reference import wf_child_payload_ref
-
-        wf_child_payload_ref(*a)
-
-    def wf_apply_out(self, *a):
-        from .reference import wf_apply_out_ref
-
-        wf_apply_out_ref(*a)
-
     def wf_hold_list(self, st, rl, ra, rg, hm, ht, hg, cursor, lm, bs, out):
         from .reference import wf_hold_list_ref
 
         wf_hold_list_ref(st, rl, ra, rg, hm, ht, hg, int(cursor), lm, bs, out)
-
-    def wf_decide(self, *a):
-        from .reference import wf_decide_ref
-
-        wf_decide_ref(*a)
 
     def materialize_rq_payload(self, payload, prev_payload, rq_src, rq_count,
                                rq_payload, stride):
@@ -577,6 +500,26 @@ class _RefOps:
         from .reference import echo_execute_ref
 
         return echo_execute_ref(ctx_arena, res_arena, int(stride))
+
+
+def _wf_forward(name: str):
+    def call(self, *a):
+        from . import reference
+
+        return getattr(reference, name + "_ref")(*a)
+
+    call.__name__ = name
+    return call
+
+
+# The workflow-engine oracles that take the extension's arguments as they are:
+# wf_X is reference.wf_X_ref. (Class attributes and not a __getattr__, so that
+# a subclass that watches attribute access sees them like any other method.)
+for _name in ("wf_sweep", "wf_expand", "wf_apply_dead", "wf_status", "wf_grant",
+              "wf_readmit", "wf_admit", "wf_cancel", "wf_journal", "wf_hold_scan",
+              "wf_settle", "wf_cond_eval", "wf_child_payload", "wf_apply_out",
+              "wf_decide"):
+    setattr(_RefOps, _name, _wf_forward(_name))
 
 
 def alloc_batch_staging(B: int, W: int, device=None, pin: bool = False):

@@ -68,9 +68,11 @@ unchanged.
 """
 from __future__ import annotations
 
+import os
+import sys
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.distributed as dist
@@ -163,6 +165,50 @@ class WfStats:
     wall_s: float = 0.0
 
 
+def _i64(mask: int) -> int:
+    """A 64-bit mask as the signed value an int64 tensor holds."""
+    return mask - (1 << 64) if mask >= (1 << 63) else mask
+
+
+class _StepRows(NamedTuple):
+    """One DAG lowered to the 64-wide host rows of the run / template tables."""
+    kind: torch.Tensor       # uint8
+    deps: torch.Tensor       # int64 step masks
+    todo: torch.Tensor       # int32 children to emit
+    maxp: torch.Tensor       # int32 for_each window
+    delay: torch.Tensor      # int32 DELAY gate
+    cond: int                # pre-evaluated CONDITION bits, signed
+    n_steps: int
+    children: int            # children of one run
+
+
+def _lower_steps(dag: DagSpec) -> _StepRows:
+    if len(dag.steps) > 64:
+        raise ValueError("device DAGs cap at 64 steps")
+    kind, deps, todo, maxp, delay = ([0] * 64 for _ in range(5))
+    cbits = 0
+    for s, spec in enumerate(dag.steps):
+        kind[s] = spec.kind
+        m = 0
+        for d in spec.deps:
+            m |= 1 << d
+        deps[s] = _i64(m)
+        if spec.kind == WFK_FOR_EACH:
+            todo[s] = spec.fanout
+        elif spec.kind == WFK_WORKER:
+            todo[s] = 1
+        if spec.kind == WFK_DELAY:
+            delay[s] = spec.delay_ticks
+        maxp[s] = spec.max_parallel
+        if spec.cond:
+            cbits |= 1 << s
+    i32 = torch.int32
+    return _StepRows(torch.tensor(kind, dtype=torch.uint8),
+                     torch.tensor(deps, dtype=torch.int64), torch.tensor(todo, dtype=i32),
+                     torch.tensor(maxp, dtype=i32), torch.tensor(delay, dtype=i32),
+                     _i64(cbits), len(dag.steps), sum(todo))
+
+
 class WorkflowPipeline:
     """Per-rank device workflow engine over a set of runs (same or mixed
     DAGs). World > 1 exchanges children over the padded all-to-all."""
@@ -211,48 +257,44 @@ class WorkflowPipeline:
         if approvals not in ("auto", "external"):
             raise ValueError("approvals must be 'auto' or 'external'")
         self.device_conditions = bool(device_conditions)
+        self.step_policy = bool(step_policy)
+        self.external = approvals == "external"
+        # every option lives in dynamic mode only
+        for on, why in (
+                (self.device_conditions, "device_conditions needs dynamic_capacity: the "
+                                         "predicates are held per template"),
+                (self.step_policy, "step_policy needs dynamic_capacity: the policy is "
+                                   "held per template"),
+                (self.external, "approvals='external' needs dynamic_capacity: a "
+                                "decision names a run by (slot, generation)"),
+                (event_cap is not None, "event_cap needs dynamic_capacity: the journal "
+                                        "reports runs by (slot, generation)")):
+            if on and dynamic_capacity is None:
+                raise ValueError(why)
         if self.device_conditions:
-            if dynamic_capacity is None:
-                raise ValueError("device_conditions needs dynamic_capacity: the "
-                                 "predicates are held per template")
             if not 1 <= int(input_words) <= 32:
                 raise ValueError("device_conditions needs 1 <= input_words <= 32")
             if int(payload_words) < int(input_words) + 2:
                 raise ValueError("device_conditions needs payload_words >= "
                                  "input_words + 2 (inputs, ordinal, step)")
             self.input_words = int(input_words)
-        elif any(s.when is not None for dg in dags for s in dg.steps):
-            raise ValueError("when needs device_conditions=True")
-        self.step_policy = bool(step_policy)
-        if self.step_policy and dynamic_capacity is None:
-            raise ValueError("step_policy needs dynamic_capacity: the policy is "
-                             "held per template")
-        self.max_retries = max_retries
-        self.timeout_cutoff = timeout_cutoff
-        for dg in dags:
-            for s in dg.steps:
-                self._check_policy(s)
-        self.external = approvals == "external"
-        if self.external and dynamic_capacity is None:
-            raise ValueError("approvals='external' needs dynamic_capacity: a "
-                             "decision names a run by (slot, generation)")
         if hold_cap is not None:
             if not self.external:
                 raise ValueError("hold_cap needs approvals='external'")
             if int(hold_cap) < 1:
                 raise ValueError("hold_cap must be >= 1")
         self.hold_cap = hold_cap
-        if not self.external and any(s.ttl_ticks for dg in dags for s in dg.steps):
-            raise ValueError("ttl_ticks needs approvals='external'")
         if event_cap is not None:
-            if dynamic_capacity is None:
-                raise ValueError("event_cap needs dynamic_capacity: the journal "
-                                 "reports runs by (slot, generation)")
             if int(event_cap) < 1:
                 raise ValueError("event_cap must be >= 1")
             event_cap = int(event_cap)
         self.event_cap = event_cap
         self.event_overflows = 0
+        self.max_retries = max_retries
+        self.timeout_cutoff = timeout_cutoff
+        for dg in dags:
+            for s in dg.steps:
+                self._check_step(s)
         device = torch.device(device)
         self.ext = _RefOps() if backend == "ref" else get_ext(required=True)
         self.device = device
@@ -287,43 +329,19 @@ class WorkflowPipeline:
         cond = torch.zeros(TN, dtype=torch.int64)
         total_children = 0
         for r, dag in enumerate(dags):
-            nsteps[r] = len(dag.steps)
-            cbits = 0
-            for s, spec in enumerate(dag.steps):
-                i = r * 64 + s
-                kinds[i] = spec.kind
-                m = 0
-                for d in spec.deps:
-                    m |= 1 << d
-                deps[i] = m - (1 << 64) if m >= (1 << 63) else m
-                if spec.kind == WFK_FOR_EACH:
-                    todo[i] = spec.fanout
-                    total_children += spec.fanout
-                elif spec.kind == WFK_WORKER:
-                    todo[i] = 1
-                    total_children += 1
-                if spec.kind == WFK_DELAY:
-                    nready[i] = spec.delay_ticks
-                maxp[i] = spec.max_parallel
-                if spec.cond:
-                    cbits |= 1 << s
-            cond[r] = cbits - (1 << 64) if cbits >= (1 << 63) else cbits
+            rows, row = _lower_steps(dag), slice(r * 64, r * 64 + 64)
+            kinds[row], deps[row], todo[row] = rows.kind, rows.deps, rows.todo
+            maxp[row], nready[row] = rows.maxp, rows.delay
+            nsteps[r], cond[r] = rows.n_steps, rows.cond
+            total_children += rows.children
         if replicate is not None:
-            st = st.repeat(NR)
-            deps = deps.repeat(NR)
-            kinds = kinds.repeat(NR)
-            todo = todo.repeat(NR)
-            maxp = maxp.repeat(NR)
-            nready = nready.repeat(NR)
-            nsteps = nsteps.repeat(NR)
-            cond = cond.repeat(NR)
+            st, deps, kinds, todo, maxp, nready, nsteps, cond = (
+                t.repeat(NR) for t in (st, deps, kinds, todo, maxp, nready, nsteps, cond))
             total_children *= NR
         if self.dynamic:
             # arena sizing only: every slot holding the widest template
-            total_children = NR * max(
-                [sum(s.fanout if s.kind == WFK_FOR_EACH else 1 for s in t.steps
-                     if s.kind in (WFK_FOR_EACH, WFK_WORKER)) for t in templates],
-                default=1)
+            total_children = NR * max([_lower_steps(t).children for t in templates],
+                                      default=1)
         self.total_children = total_children
         self._tmpl = {
             "step_state": st, "deps_mask": deps, "step_kind": kinds,
@@ -453,7 +471,13 @@ class WorkflowPipeline:
             self._appr_host_runs = self._appr_host_runs.pin_memory()
             self._appr_host_steps = self._appr_host_steps.pin_memory()
         self._pending_grants: List[tuple] = []
-        self._wf_graph = None
+        # routable slot list for pack_by_dest = child arena indices 0..C-1
+        self._iota = torch.arange(CB, dtype=torch.int32, device=d)
+        self._wf_graph = None      # None: not captured yet; (): capture failed
+        # what a tick changes on an empty table, put back after the capture's
+        # warm-up; an option appends its cumulative counters as it allocates
+        self._counters = [self.tick_buf, self.wf_counts, self.timeout_count,
+                          self.retry_count, self.admit_count, self.rq_dead]
         if device.type == "cuda":
             self._appr_h_count = torch.zeros(1, dtype=torch.int32).pin_memory()
             self._appr_ev = torch.cuda.Event()
@@ -466,7 +490,33 @@ class WorkflowPipeline:
 
     # ---- run lifecycle (dynamic mode) ---------------------------------------
     def _init_dynamic(self, templates: Sequence[DagSpec], template_cap: int) -> None:
-        d, NR, TC = self.device, self.NR, int(template_cap)
+        self._init_lifecycle(int(template_cap))
+        if self.event_cap is not None:
+            self._init_journal()
+        if self.external:
+            self._init_holds()
+        if self.step_policy:
+            self._init_policy()
+        if self.step_policy or self.device_conditions:
+            # one column serves both options. It has one spare word past the
+            # table: admit() sends the template ids of refused requests there.
+            self._run_tmpl_buf = torch.zeros(self.NR + 1, dtype=torch.int32,
+                                             device=self.device)
+            self.run_tmpl = self._run_tmpl_buf[:self.NR]
+        if self.device_conditions:
+            self._init_conditions()
+        for dag in templates:
+            self.add_template(dag)
+        # Dynamic mode warms up and captures the tick on the EMPTY table, at
+        # construction: n calls of tick() then advance the tables by exactly n
+        # ticks with the graph or without it. On an empty table the body
+        # changes only the tick counter and (never, but restored alike) the
+        # cumulative counters, which are put back.
+        if self._graph_allowed():
+            self._capture_tick()
+
+    def _init_lifecycle(self, TC: int) -> None:
+        d, NR = self.device, self.NR
         self.run_active.zero_()               # every slot starts FREE
         self.template_cap = TC
         self.n_templates = 0
@@ -495,81 +545,6 @@ class WorkflowPipeline:
         nblk = (NR + 255) // 256
         self._free_mask = torch.zeros(nblk * 4, dtype=torch.int64, device=d)
         self._blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
-        if self.event_cap is not None:
-            # journal tables. The list is one buffer, [count, pad x3 | records],
-            # so the records start 16-byte aligned for the kernel's vector
-            # stores. The shadow starts as what an empty table is: all PENDING
-            # at generation 0, which no admitted run ever has.
-            if self.event_cap + 64 * NR + 1024 > (1 << 31) - 1:
-                raise ValueError("event_cap + 64 * dynamic_capacity must stay "
-                                 "below 2^31 (the device event counter)")
-            self.ev_shadow_state = torch.zeros(NR * 64, dtype=torch.uint8, device=d)
-            self.ev_shadow_gen = torch.zeros(NR, dtype=torch.int32, device=d)
-            self._ev_buf = torch.zeros(4 + 4 * self.event_cap, dtype=torch.int32,
-                                       device=d)
-            self.ev_count = self._ev_buf[0:1]
-            self.ev_rec = self._ev_buf[4:]
-        if self.external:
-            # hold tables (see "externally decided approvals"). hold_gen starts
-            # at generation 0, which no admitted run ever has. The page buffer
-            # is [count, pad x3 | records], records 16-byte aligned.
-            if 64 * NR + 1024 > (1 << 31) - 1:
-                raise ValueError("64 * dynamic_capacity must stay below 2^31 "
-                                 "(hold keys and counts are 32-bit)")
-            if self.hold_cap is None:
-                self.hold_cap = min(64 * NR, 65536)
-            self.hold_cap = int(self.hold_cap)
-            self.tmpl_ttl = torch.zeros(TC * 64, dtype=torch.int32, device=d)
-            self._any_ttl = False
-            self.hold_mask = torch.zeros(NR, dtype=torch.int64, device=d)
-            self.hold_tick = torch.zeros(NR * 64, dtype=torch.int32, device=d)
-            self.hold_ttl = torch.zeros(NR * 64, dtype=torch.int32, device=d)
-            self.hold_gen = torch.zeros(NR, dtype=torch.int32, device=d)
-            self.hold_counts = torch.zeros(4, dtype=torch.int64, device=d)
-            self.hold_open = torch.zeros(1, dtype=torch.int32, device=d)
-            self._hold_buf = torch.zeros(4 + 4 * self.hold_cap, dtype=torch.int32,
-                                         device=d)
-            self._hold_list_mask = torch.zeros(NR, dtype=torch.int64, device=d)
-            self._hold_blk_scan = torch.zeros(nblk + 1, dtype=torch.int32, device=d)
-        if self.step_policy:
-            # policy tables (see "per-step policy"): every record starts as
-            # the pipeline's own constants, so a row can never read a zero
-            # timeout. run_tmpl has one spare word past the table: admit()
-            # sends the template ids of refused requests there.
-            if not 0 <= int(self.max_retries) <= 32767:
-                raise ValueError("step_policy needs max_retries in 0..32767")
-            if int(self.timeout_cutoff) < 1:
-                raise ValueError("step_policy needs timeout_cutoff >= 1")
-            stock = RetrySpec(int(self.max_retries))
-            self.tmpl_policy = torch.tensor(
-                [stock.max_retries, stock.backoff_ticks, stock.cap_ticks,
-                 stock.multiplier_q8], dtype=torch.int32).repeat(TC * 64).to(d)
-            self.tmpl_timeout = torch.full((TC * 64,), int(self.timeout_cutoff),
-                                           dtype=torch.int32, device=d)
-        if self.step_policy or self.device_conditions:
-            # one column serves both options
-            self._run_tmpl_buf = torch.zeros(NR + 1, dtype=torch.int32, device=d)
-            self.run_tmpl = self._run_tmpl_buf[:NR]
-        if self.device_conditions:
-            # see "conditions decided on the device". run_input and step_out
-            # have one spare row past the table, as run_tmpl has a spare word:
-            # admit() sends the rows of refused requests there.
-            IW = self.input_words
-            self._run_input_buf = torch.zeros((NR + 1) * IW, dtype=torch.int32, device=d)
-            self.run_input = self._run_input_buf[:NR * IW]
-            self._step_out_buf = torch.zeros((NR + 1) * 64, dtype=torch.int32, device=d)
-            self.step_out = self._step_out_buf[:NR * 64]
-            self.tmpl_cond = torch.zeros(TC * 64 * 4, dtype=torch.int32, device=d)
-            self.tmpl_cond_mask = torch.zeros(TC, dtype=torch.int64, device=d)
-            # 1 where the template's step is a CONDITION without a predicate:
-            # its output word is the admitted bit, written by admit()
-            self._tmpl_plain_cond = torch.zeros(TC * 64, dtype=torch.int32, device=d)
-            self._bit_idx = torch.arange(64, dtype=torch.int64, device=d)
-            self._any_plain_cond = False
-            self.cond_counts = torch.zeros(2, dtype=torch.int64, device=d)
-        for dag in templates:
-            self.add_template(dag)
-        self._capture_dynamic()
 
     # ---- per-step policy (dynamic mode, step_policy=True) --------------------
     # Retry, backoff and timeout are properties of a step, held per template
@@ -594,6 +569,34 @@ class WorkflowPipeline:
     # A FREE row can therefore hold a DISPATCHED step whose longer timeout
     # has not run out; wf_settle skips FREE rows.
     _POLICY_KINDS = (WFK_WORKER, WFK_FOR_EACH)
+
+    def _init_policy(self) -> None:
+        # every record starts as the pipeline's own constants, so a row can
+        # never read a zero timeout
+        d, TC = self.device, self.template_cap
+        if not 0 <= int(self.max_retries) <= 32767:
+            raise ValueError("step_policy needs max_retries in 0..32767")
+        if int(self.timeout_cutoff) < 1:
+            raise ValueError("step_policy needs timeout_cutoff >= 1")
+        stock = RetrySpec(int(self.max_retries))
+        self.tmpl_policy = torch.tensor(
+            [stock.max_retries, stock.backoff_ticks, stock.cap_ticks,
+             stock.multiplier_q8], dtype=torch.int32).repeat(TC * 64).to(d)
+        self.tmpl_timeout = torch.full((TC * 64,), int(self.timeout_cutoff),
+                                       dtype=torch.int32, device=d)
+
+    def _add_policy_rows(self, t: int, dag: DagSpec) -> None:
+        stock = RetrySpec(int(self.max_retries))
+        pol, tmo = [], []
+        for s in range(64):
+            sp = dag.steps[s] if s < len(dag.steps) else None
+            r = sp.retry if sp is not None and sp.retry is not None else stock
+            pol += [int(r.max_retries), int(r.backoff_ticks), int(r.cap_ticks),
+                    int(r.multiplier_q8)]
+            tmo.append(int(sp.timeout_ticks) if sp is not None and sp.timeout_ticks
+                       else int(self.timeout_cutoff))
+        self.tmpl_policy[t * 256:t * 256 + 256].copy_(torch.tensor(pol, dtype=torch.int32))
+        self.tmpl_timeout[t * 64:t * 64 + 64].copy_(torch.tensor(tmo, dtype=torch.int32))
 
     # ---- conditions decided on the device (dynamic mode, device_conditions) --
     # Tables, allocated only with the option on:
@@ -620,6 +623,52 @@ class WorkflowPipeline:
     # A CONDITION without a predicate keeps its admitted bit, and admit()
     # writes that bit as its output word.
     _OUT_KINDS = (WFK_WORKER, WFK_FOR_EACH, WFK_CONDITION)
+
+    def _init_conditions(self) -> None:
+        # run_input and step_out have one spare row past the table, as
+        # run_tmpl has a spare word: admit() sends the rows of refused
+        # requests there.
+        d, NR, TC, IW = self.device, self.NR, self.template_cap, self.input_words
+        self._run_input_buf = torch.zeros((NR + 1) * IW, dtype=torch.int32, device=d)
+        self.run_input = self._run_input_buf[:NR * IW]
+        self._step_out_buf = torch.zeros((NR + 1) * 64, dtype=torch.int32, device=d)
+        self.step_out = self._step_out_buf[:NR * 64]
+        self.tmpl_cond = torch.zeros(TC * 64 * 4, dtype=torch.int32, device=d)
+        self.tmpl_cond_mask = torch.zeros(TC, dtype=torch.int64, device=d)
+        # 1 where the template's step is a CONDITION without a predicate:
+        # its output word is the admitted bit, written by admit()
+        self._tmpl_plain_cond = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+        self._bit_idx = torch.arange(64, dtype=torch.int64, device=d)
+        self._any_plain_cond = False
+        self.cond_counts = torch.zeros(2, dtype=torch.int64, device=d)
+        self._counters.append(self.cond_counts)
+
+    def _add_cond_rows(self, t: int, dag: DagSpec, cond_recs: dict) -> None:
+        rec, cm = [0] * 256, 0
+        for s, r4 in cond_recs.items():
+            rec[4 * s:4 * s + 4] = r4
+            cm |= 1 << s
+        self.tmpl_cond[t * 256:t * 256 + 256].copy_(torch.tensor(rec, dtype=torch.int32))
+        self.tmpl_cond_mask[t:t + 1].fill_(_i64(cm))
+        plain = [int(s < len(dag.steps) and dag.steps[s].kind == WFK_CONDITION
+                     and dag.steps[s].when is None) for s in range(64)]
+        self._tmpl_plain_cond[t * 64:t * 64 + 64].copy_(
+            torch.tensor(plain, dtype=torch.int32))
+        self._any_plain_cond = self._any_plain_cond or any(plain)
+
+    def _admit_cond_rows(self, dst, tmpl, cond, inputs) -> None:
+        """Input row and output row of the runs just admitted; `dst` as in
+        admit(). The outputs start at zero, but for a CONDITION step without
+        a predicate: its output is the bit it was admitted with."""
+        dst = dst.long()
+        self._run_input_buf.view(-1, self.input_words)[dst] = \
+            inputs.view(-1, self.input_words)
+        if self._any_plain_cond:
+            bits = (cond[:, None] >> self._bit_idx[None, :]) & 1
+            self._step_out_buf.view(-1, 64)[dst] = \
+                bits.to(torch.int32) * self._tmpl_plain_cond.view(-1, 64)[tmpl.long()]
+        else:       # no template has such a step: fewer launches per admit
+            self._step_out_buf.view(-1, 64)[dst] = 0
 
     def _cond_record(self, dag: DagSpec, s: int) -> List[int]:
         """Validated (code, a, b, imm) of step s's predicate."""
@@ -670,6 +719,22 @@ class WorkflowPipeline:
         c = self.cond_counts.cpu().tolist()
         return {"true": c[0], "false": c[1]}
 
+    def _check_step(self, spec: StepSpec, arena: Optional[int] = None) -> None:
+        """Every check of one StepSpec against the pipeline's options; `arena`
+        is the child arena a template's fan-out has to fit."""
+        if arena is not None and spec.kind == WFK_FOR_EACH and spec.fanout > arena:
+            raise ValueError(f"fanout {spec.fanout} can never be emitted "
+                             f"(child arena {arena})")
+        if spec.ttl_ticks:
+            if not self.external:
+                raise ValueError("ttl_ticks needs approvals='external'")
+            if spec.kind != WFK_APPROVAL or spec.ttl_ticks < 0:
+                raise ValueError("ttl_ticks is a positive tick count on an "
+                                 "APPROVAL step")
+        self._check_policy(spec)
+        if spec.when is not None and not self.device_conditions:
+            raise ValueError("when needs device_conditions=True")
+
     def _check_policy(self, spec: StepSpec) -> None:
         if spec.retry is None and not spec.timeout_ticks:
             return
@@ -703,85 +768,28 @@ class WorkflowPipeline:
     def add_template(self, dag: DagSpec) -> int:
         """Register one more workflow template; returns its id."""
         self._require_dynamic(True, "add_template")
-        if len(dag.steps) > 64:
-            raise ValueError("device DAGs cap at 64 steps")
+        rows = _lower_steps(dag)
         t = self.n_templates
         if t >= self.template_cap:
             raise ValueError(f"template table full ({self.template_cap})")
         for spec in dag.steps:
-            if spec.kind == WFK_FOR_EACH and spec.fanout > self.CB:
-                raise ValueError(f"fanout {spec.fanout} can never be emitted "
-                                 f"(child arena {self.CB})")
-            if spec.ttl_ticks:
-                if not self.external:
-                    raise ValueError("ttl_ticks needs approvals='external'")
-                if spec.kind != WFK_APPROVAL or spec.ttl_ticks < 0:
-                    raise ValueError("ttl_ticks is a positive tick count on an "
-                                     "APPROVAL step")
-            self._check_policy(spec)
-            if spec.when is not None and not self.device_conditions:
-                raise ValueError("when needs device_conditions=True")
+            self._check_step(spec, arena=self.CB)
         cond_recs = {s: self._cond_record(dag, s) for s, sp in enumerate(dag.steps)
                      if sp.when is not None}
-        deps = torch.zeros(64, dtype=torch.int64)
-        kinds = torch.zeros(64, dtype=torch.uint8)
-        todo = torch.zeros(64, dtype=torch.int32)
-        maxp = torch.zeros(64, dtype=torch.int32)
-        delay = torch.zeros(64, dtype=torch.int32)
-        cbits = 0
-        for s, spec in enumerate(dag.steps):
-            kinds[s] = spec.kind
-            m = 0
-            for dep in spec.deps:
-                m |= 1 << dep
-            deps[s] = m - (1 << 64) if m >= (1 << 63) else m
-            if spec.kind == WFK_FOR_EACH:
-                todo[s] = spec.fanout
-            elif spec.kind == WFK_WORKER:
-                todo[s] = 1
-            if spec.kind == WFK_DELAY:
-                delay[s] = spec.delay_ticks
-            maxp[s] = spec.max_parallel
-            if spec.cond:
-                cbits |= 1 << s
         row = slice(t * 64, t * 64 + 64)
-        self.tmpl_deps[row].copy_(deps)
-        self.tmpl_kind[row].copy_(kinds)
-        self.tmpl_todo[row].copy_(todo)
-        self.tmpl_maxp[row].copy_(maxp)
-        self.tmpl_delay[row].copy_(delay)
-        self.tmpl_nsteps[t:t + 1].fill_(len(dag.steps))
+        self.tmpl_deps[row].copy_(rows.deps)
+        self.tmpl_kind[row].copy_(rows.kind)
+        self.tmpl_todo[row].copy_(rows.todo)
+        self.tmpl_maxp[row].copy_(rows.maxp)
+        self.tmpl_delay[row].copy_(rows.delay)
+        self.tmpl_nsteps[t:t + 1].fill_(rows.n_steps)
         if self.external:
-            ttl = torch.tensor([sp.ttl_ticks for sp in dag.steps]
-                               + [0] * (64 - len(dag.steps)), dtype=torch.int32)
-            self.tmpl_ttl[row].copy_(ttl)
-            self._any_ttl = self._any_ttl or bool(ttl.any())
+            self._add_ttl_row(t, dag)
         if self.step_policy:
-            stock = RetrySpec(int(self.max_retries))
-            pol, tmo = [], []
-            for s in range(64):
-                sp = dag.steps[s] if s < len(dag.steps) else None
-                r = sp.retry if sp is not None and sp.retry is not None else stock
-                pol += [int(r.max_retries), int(r.backoff_ticks), int(r.cap_ticks),
-                        int(r.multiplier_q8)]
-                tmo.append(int(sp.timeout_ticks) if sp is not None and sp.timeout_ticks
-                           else int(self.timeout_cutoff))
-            self.tmpl_policy[t * 256:t * 256 + 256].copy_(
-                torch.tensor(pol, dtype=torch.int32))
-            self.tmpl_timeout[row].copy_(torch.tensor(tmo, dtype=torch.int32))
+            self._add_policy_rows(t, dag)
         if self.device_conditions:
-            rec, cm = [0] * 256, 0
-            for s, r4 in cond_recs.items():
-                rec[4 * s:4 * s + 4] = r4
-                cm |= 1 << s
-            self.tmpl_cond[t * 256:t * 256 + 256].copy_(
-                torch.tensor(rec, dtype=torch.int32))
-            self.tmpl_cond_mask[t:t + 1].fill_(cm - (1 << 64) if cm >= (1 << 63) else cm)
-            plain = [int(s < len(dag.steps) and dag.steps[s].kind == WFK_CONDITION
-                         and dag.steps[s].when is None) for s in range(64)]
-            self._tmpl_plain_cond[row].copy_(torch.tensor(plain, dtype=torch.int32))
-            self._any_plain_cond = self._any_plain_cond or any(plain)
-        self._tmpl_cond.append(cbits - (1 << 64) if cbits >= (1 << 63) else cbits)
+            self._add_cond_rows(t, dag, cond_recs)
+        self._tmpl_cond.append(rows.cond)
         self.n_templates = t + 1
         return t
 
@@ -791,6 +799,43 @@ class WorkflowPipeline:
         `inputs[i]` (device_conditions) holds at most input_words ints in
         int32 range, zero padded: the run's input words."""
         self._require_dynamic(True, "admit")
+        n, req = self._pack_request(templates, cond_bits, fanout, inputs)
+        if n == 0:
+            return [], []
+        req = req.to(self.device)         # the one H2D
+        cond, tmpl = req[:2 * n].view(torch.int64), req[2 * n:3 * n]
+        fanout, inputs = req[3 * n:4 * n], req[4 * n:]
+        out = torch.empty(2 * n, dtype=torch.int32, device=self.device)
+        slots = out[:n]
+        self.ext.wf_admit(
+            tmpl, cond, fanout,
+            self.tmpl_deps, self.tmpl_kind, self.tmpl_todo, self.tmpl_maxp,
+            self.tmpl_delay, self.tmpl_nsteps,
+            self.step_state, self.step_attempts, self.deps_mask, self.step_kind,
+            self.children_todo, self.max_parallel, self.children_out,
+            self.children_done, self.children_fail, self.children_emitted,
+            self.next_ready, self.dispatch_tick, self.n_steps, self.cond_bits,
+            self.run_state, self.run_active, self.run_life, self.run_gen,
+            self.tick_buf, self._free_mask, self._blk_scan,
+            slots, out[n:], self.admit_count)
+        if self.step_policy or self.device_conditions:
+            # run_tmpl is a run column wf_admit does not know: one indexed
+            # store of the accepted requests' template ids. A refused request
+            # has slot -1, and -1 mod (NR + 1) = NR is the spare word past the
+            # table, so no mask and no host round trip is needed.
+            dst = torch.remainder(slots, self.NR + 1)
+            self._run_tmpl_buf[dst] = tmpl
+            if self.device_conditions:
+                # the same trick for the run's input row and its output row
+                self._admit_cond_rows(dst, tmpl, cond, inputs)
+        if self.external and self._any_ttl:
+            self._admit_hold_ttl(slots, tmpl)
+        h = out.cpu()                     # the one D2H (synchronising)
+        return h[:n].tolist(), h[n:].tolist()
+
+    def _pack_request(self, templates, cond_bits, fanout, inputs):
+        """Validated admit() request as (n, one host buffer): [cond as int64 |
+        template ids | fanouts | input rows]."""
         tl = [int(t) for t in templates]
         n = len(tl)
         for t in tl:
@@ -804,8 +849,7 @@ class WorkflowPipeline:
         if cond_bits is None:
             cl = [self._tmpl_cond[t] for t in tl]
         else:
-            cl = [int(c) - (1 << 64) if int(c) >= (1 << 63) else int(c)
-                  for c in cond_bits]
+            cl = [_i64(int(c)) for c in cond_bits]
         if len(fl) != n or len(cl) != n:
             raise ValueError("cond_bits / fanout must match templates in length")
         IW = self.input_words if self.device_conditions else 0
@@ -825,56 +869,14 @@ class WorkflowPipeline:
                         raise ValueError(f"input word {v!r} is not an int32")
                 il += list(r) + [0] * (IW - len(r))
         if n == 0:
-            return [], []
-        # one H2D: [cond as int64 | template ids | fanouts | inputs] in one buffer
+            return 0, None
         req = torch.empty(4 * n + n * IW, dtype=torch.int32)
         if IW:
             req[4 * n:] = torch.tensor(il, dtype=torch.int32)
         req[:2 * n].view(torch.int64).copy_(torch.tensor(cl, dtype=torch.int64))
         req[2 * n:3 * n] = torch.tensor(tl, dtype=torch.int32)
         req[3 * n:4 * n] = torch.tensor(fl, dtype=torch.int32)
-        req = req.to(self.device)
-        out = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-        self.ext.wf_admit(
-            req[2 * n:3 * n], req[:2 * n].view(torch.int64), req[3 * n:4 * n],
-            self.tmpl_deps, self.tmpl_kind, self.tmpl_todo, self.tmpl_maxp,
-            self.tmpl_delay, self.tmpl_nsteps,
-            self.step_state, self.step_attempts, self.deps_mask, self.step_kind,
-            self.children_todo, self.max_parallel, self.children_out,
-            self.children_done, self.children_fail, self.children_emitted,
-            self.next_ready, self.dispatch_tick, self.n_steps, self.cond_bits,
-            self.run_state, self.run_active, self.run_life, self.run_gen,
-            self.tick_buf, self._free_mask, self._blk_scan,
-            out[:n], out[n:], self.admit_count)
-        if self.step_policy or self.device_conditions:
-            # run_tmpl is a run column wf_admit does not know: one indexed
-            # store of the accepted requests' template ids. A refused request
-            # has slot -1, and -1 mod (NR + 1) = NR is the spare word past the
-            # table, so no mask and no host round trip is needed.
-            dst = torch.remainder(out[:n], self.NR + 1)
-            self._run_tmpl_buf[dst] = req[2 * n:3 * n]
-        if self.device_conditions:
-            # the same trick for the run's input row and its output row. The
-            # outputs start at zero, but for a CONDITION step without a
-            # predicate: its output is the bit it was admitted with.
-            dst = dst.long()
-            self._run_input_buf.view(-1, IW)[dst] = req[4 * n:].view(n, IW)
-            if self._any_plain_cond:
-                bits = (req[:2 * n].view(torch.int64)[:, None] >> self._bit_idx[None, :]) & 1
-                self._step_out_buf.view(-1, 64)[dst] = \
-                    bits.to(torch.int32) \
-                    * self._tmpl_plain_cond.view(-1, 64)[req[2 * n:3 * n].long()]
-            else:       # no template has such a step: fewer launches per admit
-                self._step_out_buf.view(-1, 64)[dst] = 0
-        if self.external and self._any_ttl:
-            # hold_ttl is a run column like max_parallel: the template's row
-            # goes into every slot just filled (all zero until a template
-            # carries a ttl, so nothing to copy before that)
-            ok = out[:n] >= 0
-            self.hold_ttl.view(-1, 64)[out[:n][ok].long()] = \
-                self.tmpl_ttl.view(-1, 64)[req[2 * n:3 * n][ok].long()]
-        h = out.cpu()
-        return h[:n].tolist(), h[n:].tolist()
+        return n, req
 
     def cancel(self, slots: Sequence[int], gens: Sequence[int]) -> List[int]:
         """Cancel the runs named by (slot, gen) handles; returns 1 per request
@@ -944,6 +946,22 @@ class WorkflowPipeline:
     #   (to a later pass, with that pass's stamp) and loses none, provided
     #   the list is drained before the run's slot is released: a FREE row is
     #   not journaled, so drain events before drain_completed().
+    def _init_journal(self) -> None:
+        # The list is one buffer, [count, pad x3 | records], so the records
+        # start 16-byte aligned for the kernel's vector stores. The shadow
+        # starts as what an empty table is: all PENDING at generation 0,
+        # which no admitted run ever has.
+        d, NR = self.device, self.NR
+        if self.event_cap + 64 * NR + 1024 > (1 << 31) - 1:
+            raise ValueError("event_cap + 64 * dynamic_capacity must stay "
+                             "below 2^31 (the device event counter)")
+        self.ev_shadow_state = torch.zeros(NR * 64, dtype=torch.uint8, device=d)
+        self.ev_shadow_gen = torch.zeros(NR, dtype=torch.int32, device=d)
+        self._ev_buf = torch.zeros(4 + 4 * self.event_cap, dtype=torch.int32, device=d)
+        self.ev_count = self._ev_buf[0:1]
+        self.ev_rec = self._ev_buf[4:]
+        self._counters.append(self.ev_count)
+
     def _require_events(self, what: str) -> None:
         self._require_dynamic(True, what)
         if self.event_cap is None:
@@ -1009,6 +1027,44 @@ class WorkflowPipeline:
     # - decide() writes the one state byte; the next scan closes the hold, and
     #   open_holds() filters on the state, so a decided hold is gone at once.
     # The tables are rank-local; world > 1 runs the same scan eagerly.
+    def _init_holds(self) -> None:
+        # hold_gen starts at generation 0, which no admitted run ever has. The
+        # page buffer is [count, pad x3 | records], records 16-byte aligned.
+        d, NR, TC = self.device, self.NR, self.template_cap
+        if 64 * NR + 1024 > (1 << 31) - 1:
+            raise ValueError("64 * dynamic_capacity must stay below 2^31 "
+                             "(hold keys and counts are 32-bit)")
+        if self.hold_cap is None:
+            self.hold_cap = min(64 * NR, 65536)
+        self.hold_cap = int(self.hold_cap)
+        self.tmpl_ttl = torch.zeros(TC * 64, dtype=torch.int32, device=d)
+        self._any_ttl = False
+        self.hold_mask = torch.zeros(NR, dtype=torch.int64, device=d)
+        self.hold_tick = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+        self.hold_ttl = torch.zeros(NR * 64, dtype=torch.int32, device=d)
+        self.hold_gen = torch.zeros(NR, dtype=torch.int32, device=d)
+        self.hold_counts = torch.zeros(4, dtype=torch.int64, device=d)
+        self.hold_open = torch.zeros(1, dtype=torch.int32, device=d)
+        self._hold_buf = torch.zeros(4 + 4 * self.hold_cap, dtype=torch.int32, device=d)
+        self._hold_list_mask = torch.zeros(NR, dtype=torch.int64, device=d)
+        self._hold_blk_scan = torch.zeros((NR + 255) // 256 + 1, dtype=torch.int32,
+                                          device=d)
+        self._counters += [self.hold_counts, self.hold_open]
+
+    def _add_ttl_row(self, t: int, dag: DagSpec) -> None:
+        ttl = torch.tensor([sp.ttl_ticks for sp in dag.steps]
+                           + [0] * (64 - len(dag.steps)), dtype=torch.int32)
+        self.tmpl_ttl[t * 64:t * 64 + 64].copy_(ttl)
+        self._any_ttl = self._any_ttl or bool(ttl.any())
+
+    def _admit_hold_ttl(self, slots, tmpl) -> None:
+        # hold_ttl is a run column like max_parallel: the template's row goes
+        # into every slot just filled (all zero until a template carries a
+        # ttl, so nothing to copy before that)
+        ok = slots >= 0
+        self.hold_ttl.view(-1, 64)[slots[ok].long()] = \
+            self.tmpl_ttl.view(-1, 64)[tmpl[ok].long()]
+
     def _require_external(self, what: str) -> None:
         self._require_dynamic(True, what)
         if not self.external:
@@ -1076,53 +1132,13 @@ class WorkflowPipeline:
         return {"opened": c[0], "expired": c[1], "approved": c[2],
                 "rejected": c[3], "open": int(self.hold_open.cpu()[0])}
 
-    def _capture_dynamic(self) -> None:
-        """Dynamic mode warms up and captures the tick on the EMPTY table, at
-        construction: n calls of tick() then advance the tables by exactly n
-        ticks with the graph or without it. On an empty table the body
-        changes only the tick counter and (never, but restored alike) the
-        cumulative counters, which are put back."""
-        import os
-
-        if self.device.type != "cuda" or self.world > 1 \
-                or os.environ.get("CORDUM_WF_NO_GRAPH"):
-            return
-        counters = [self.tick_buf, self.wf_counts, self.timeout_count,
-                    self.retry_count, self.admit_count, self.rq_dead]
-        if self.event_cap is not None:
-            counters.append(self.ev_count)
-        if self.external:
-            counters += [self.hold_counts, self.hold_open]
-        if self.device_conditions:
-            counters.append(self.cond_counts)
-        saved = [(t, t.clone()) for t in counters]
-        for _ in range(2):
-            self._tick_device_body()
-        torch.cuda.synchronize(self.device)
-        try:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._tick_device_body()
-            self._wf_graph = g
-        except Exception as e:
-            import sys
-
-            print(f"[cordum] wf-graph capture failed, running eager: {e!r}",
-                  file=sys.stderr)
-            self._wf_graph = ()
-        for t, v in saved:
-            t.copy_(v)
-        torch.cuda.synchronize(self.device)
-
     # ---- run admission -------------------------------------------------------
     def reset_runs(self) -> None:
         """Re-admit the whole run wave: copy the creation image back into the
         device tables (this is the honest run-creation H2D cost when the
         template lives on the host; templates are staged once)."""
         self._require_dynamic(False, "reset_runs")
-        if not hasattr(self, "_tmpl_dev"):
-            self._tmpl_dev = {k: v.to(self.device) for k, v in self._tmpl.items()}
-        t = self._tmpl_dev
+        t = self._ensure_tmpl_dev()
         self.step_state.copy_(t["step_state"])
         self.children_todo.copy_(t["children_todo"])
         self.next_ready.copy_(t["next_ready"])
@@ -1246,7 +1262,7 @@ class WorkflowPipeline:
                          self.rq_src, self.rq_widx, self.rq_attempts,
                          self.rq_count, self.rq_dead,
                          self.dead_src, self.dead_count)
-        ext.pack_by_dest(self._child_slots(), self.child_widx, self.child_count,
+        ext.pack_by_dest(self._iota, self.child_widx, self.child_count,
                          self.pad_send_slots, self.pad_send_widx, self.pad_send_cnt,
                          self.NWL, cap, self.CB,
                          self.rq_src, self.rq_widx, self.rq_attempts,
@@ -1320,21 +1336,15 @@ class WorkflowPipeline:
             # tick of lag)
             self._appr_h_count.copy_(self.appr_count, non_blocking=True)
 
-    def _ensure_wf_graph(self) -> bool:
-        import os
+    def _graph_allowed(self) -> bool:
+        return self.device.type == "cuda" and self.world == 1 \
+            and not os.environ.get("CORDUM_WF_NO_GRAPH")
 
-        if self.device.type != "cuda" or self.world > 1 \
-                or os.environ.get("CORDUM_WF_NO_GRAPH"):
-            return False
-        if self._wf_graph is not None:
-            return True
-        # eager warmup (allocator steady state), then capture; the warmup
-        # ran for real, so restore the run tables (reset) and the cumulative
-        # counters (snapshot) afterwards — the triggering tick then replays
-        # as tick 0 of a fresh wave
-        saved = [(t, t.clone()) for t in
-                 (self.wf_counts, self.timeout_count, self.retry_count,
-                  self.admit_count, self.rq_dead)]
+    def _capture_tick(self) -> None:
+        """Eager warm-up (allocator steady state), then capture of the tick
+        body into _wf_graph, () if that fails. The warm-up ran for real: the
+        counters an option registered are put back afterwards."""
+        saved = [(t, t.clone()) for t in self._counters]
         for _ in range(2):
             self._tick_device_body()
         torch.cuda.synchronize(self.device)
@@ -1344,19 +1354,33 @@ class WorkflowPipeline:
                 self._tick_device_body()
             self._wf_graph = g
         except Exception as e:
-            import sys
-
             print(f"[cordum] wf-graph capture failed, running eager: {e!r}",
                   file=sys.stderr)
             self._wf_graph = ()
-        self.reset_runs()
         for t, v in saved:
             t.copy_(v)
         torch.cuda.synchronize(self.device)
-        return bool(self._wf_graph)
+
+    def _run_body(self) -> None:
+        """One tick body: the captured graph where there is one, else eager."""
+        if not self.dynamic:
+            # static mode captures on its first tick; the warm-up changed the
+            # run tables too, so the wave is reset and the triggering tick
+            # replays as tick 0 of a fresh one. (Dynamic mode captured at
+            # construction, on the empty table.)
+            if not self._graph_allowed():
+                return self._tick_device_body()
+            if self._wf_graph is None:
+                self._capture_tick()
+                self.reset_runs()
+        if self._wf_graph:
+            self._wf_graph.replay()
+        else:
+            self._tick_device_body()
 
     def _drain_approvals(self) -> None:
-        na = int(self._appr_h_count[0]) if self._appr_h_count is not None             else int(self.appr_count.cpu()[0])
+        na = int(self._appr_h_count[0]) if self._appr_h_count is not None \
+            else int(self.appr_count.cpu()[0])
         if na > 0:
             na = min(na, self.NR)
             self._pending_grants.append(
@@ -1366,41 +1390,31 @@ class WorkflowPipeline:
         ext = self.ext
         self._tick += 1
 
-        if self.external:
-            # no host hop: holds wait in the tables for decide(). Nothing is
-            # granted, drained or polled here.
-            if self.device.type == "cuda" and self.world == 1 and bool(self._wf_graph):
-                self._wf_graph.replay()
-            else:
-                self._tick_device_body()
-            self._refresh_order()
-            return
+        # external approvals have no host hop: holds wait in the tables for
+        # decide(). Nothing is granted, drained or polled here.
+        if not self.external:
+            # a drain deferred from last tick (its D2H event was still in
+            # flight) MUST land before this tick's body overwrites the approval
+            # ring — by now the event has long completed, so this rarely blocks
+            if getattr(self, "_appr_deferred", False):
+                self._appr_ev.synchronize()
+                self._drain_approvals()
+                self._appr_deferred = False
 
-        # a drain deferred from last tick (its D2H event was still in
-        # flight) MUST land before this tick's body overwrites the approval
-        # ring — by now the event has long completed, so this rarely blocks
-        if getattr(self, "_appr_deferred", False):
-            self._appr_ev.synchronize()
-            self._drain_approvals()
-            self._appr_deferred = False
+            # host hop: approvals drained LAST tick are granted now (1-tick
+            # admin latency, like the reference's async approve endpoint)
+            if self._pending_grants:
+                runs, steps = self._pending_grants.pop()
+                n = runs.shape[0]
+                v = torch.full((n,), self.approval_verdict, dtype=torch.uint8,
+                               device=self.device)
+                ext.wf_grant(runs.to(self.device), steps.to(self.device), v, n,
+                             self.step_state)
 
-        # host hop: approvals drained LAST tick are granted now (1-tick
-        # admin latency, like the reference's async approve endpoint)
-        if self._pending_grants:
-            runs, steps = self._pending_grants.pop()
-            n = runs.shape[0]
-            v = torch.full((n,), self.approval_verdict, dtype=torch.uint8,
-                           device=self.device)
-            ext.wf_grant(runs.to(self.device), steps.to(self.device), v, n,
-                         self.step_state)
-
-        # dynamic mode captured at construction, on the empty table
-        if self.device.type == "cuda" and self.world == 1 and (
-                bool(self._wf_graph) if self.dynamic else self._ensure_wf_graph()):
-            self._wf_graph.replay()
-        else:
-            self._tick_device_body()
+        self._run_body()
         self._refresh_order()
+        if self.external:
+            return
 
         # drain fresh approval holds for next tick's grant. On GPU the count
         # arrives via the in-body pinned D2H; poll non-blockingly — if the
@@ -1411,15 +1425,7 @@ class WorkflowPipeline:
             if not self._appr_ev.query():
                 self._appr_deferred = True
                 return
-            self._drain_approvals()
-        else:
-            self._drain_approvals()
-
-    def _child_slots(self):
-        """Routable slot list for pack_by_dest = child arena indices 0..C-1."""
-        if not hasattr(self, "_iota"):
-            self._iota = torch.arange(self.CB, dtype=torch.int32, device=self.device)
-        return self._iota
+        self._drain_approvals()
 
     # ---- continuous mode (config #5) ----------------------------------------
     def _ensure_tmpl_dev(self):
@@ -1427,10 +1433,7 @@ class WorkflowPipeline:
             self._tmpl_dev = {k: v.to(self.device) for k, v in self._tmpl.items()}
         return self._tmpl_dev
 
-    def readmit_succeeded(self) -> None:
-        """Terminal SUCCEEDED runs re-enter from the creation template so the
-        table stays full (config #5 'hold 1M concurrent runs')."""
-        self._require_dynamic(False, "readmit_succeeded")
+    def _readmit(self, filter_state: int) -> None:
         t = self._ensure_tmpl_dev()
         self.ext.wf_readmit(self.run_active, self.run_state, self.n_steps,
                             self.step_state, self.step_attempts,
@@ -1438,7 +1441,13 @@ class WorkflowPipeline:
                             self.children_done, self.children_fail,
                             self.children_emitted, self.next_ready,
                             self.dispatch_tick, t["children_todo"],
-                            t["next_ready"], WFS_SUCCEEDED, self.admit_count)
+                            t["next_ready"], filter_state, self.admit_count)
+
+    def readmit_succeeded(self) -> None:
+        """Terminal SUCCEEDED runs re-enter from the creation template so the
+        table stays full (config #5 'hold 1M concurrent runs')."""
+        self._require_dynamic(False, "readmit_succeeded")
+        self._readmit(WFS_SUCCEEDED)
 
     def drain_failed_to_dlq(self, dlq=None) -> int:
         """Host DLQ drain (dlq_store.go analog): record every FAILED run,
@@ -1461,14 +1470,7 @@ class WorkflowPipeline:
                                  last_state="FAILED",
                                  attempts=self.max_retries))
         if n:
-            t = self._ensure_tmpl_dev()
-            self.ext.wf_readmit(self.run_active, self.run_state, self.n_steps,
-                                self.step_state, self.step_attempts,
-                                self.children_todo, self.children_out,
-                                self.children_done, self.children_fail,
-                                self.children_emitted, self.next_ready,
-                                self.dispatch_tick, t["children_todo"],
-                                t["next_ready"], WFS_FAILED, self.admit_count)
+            self._readmit(WFS_FAILED)
         return n
 
     # ---- wave driver ---------------------------------------------------------
