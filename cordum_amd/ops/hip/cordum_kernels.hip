@@ -602,6 +602,119 @@ __global__ __launch_bounds__(BLOCK) void dlq_ring_append_kernel(
     if (pos >= 0) ring[pos % ring_size] = live ? slots[i] : -1;
 }
 
+// ---------------------------------------------------------------------------
+// Row-scan helpers of the run/step tables (K3, K3-WF)
+// ---------------------------------------------------------------------------
+// A run is one row of 64 steps; the step states are one byte each, 64 bytes
+// per row. The row-scan kernels (wf_journal, wf_settle, wf_cond_eval,
+// wf_hold_scan) give a row 4 lanes: lane q of row r owns steps 16q .. 16q+15,
+// which are one 16-byte load at r*64 + q*16, so a wave covers 16 rows, a block
+// 64, and the grid is ceil(NR*4 / BLOCK). The four lanes of a row are
+// neighbours (lanes 4k .. 4k+3 of a wave). A lane keeps its 16 bytes as four
+// words, step 16q+j in byte j&3 of word j>>2, works on 16-bit masks with bit j
+// for step 16q+j, and stores the 16 bytes back, as one store, only if one
+// changed. Per-block counters: the waves' totals are summed through LDS and
+// thread 0 adds them, one atomic per counter and block, not per wave: when
+// most waves of a large table have something to add, adds to one word are
+// served one after the other.
+struct wf_bytes16 { unsigned w[4]; };
+struct wf_row_lane { int r, q; size_t off; };       // row, quarter, byte offset of the 16
+
+__device__ __forceinline__ wf_row_lane wf_row_coords() {
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    return {t >> 2, t & 3, (size_t)(t >> 2) * 64 + (size_t)(t & 3) * 16};
+}
+__device__ __forceinline__ wf_bytes16 load16(const unsigned char* p) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    return {{v.x, v.y, v.z, v.w}};
+}
+__device__ __forceinline__ unsigned byte16(const wf_bytes16& b, int j) {
+    return (b.w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+}
+// bit j: pred(byte j)
+template <class Pred>
+__device__ __forceinline__ unsigned mask16(const wf_bytes16& b, Pred pred) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m |= (unsigned)pred(byte16(b, j)) << j;
+    return m;
+}
+// bit j: byte j == value
+__device__ __forceinline__ unsigned match16(const wf_bytes16& b, unsigned value) {
+    return mask16(b, [=](unsigned x) { return x == value; });
+}
+// bit j: byte j of a != byte j of b
+__device__ __forceinline__ unsigned differ16(const wf_bytes16& a, const wf_bytes16& b) {
+    const wf_bytes16 x = {{a.w[0] ^ b.w[0], a.w[1] ^ b.w[1], a.w[2] ^ b.w[2], a.w[3] ^ b.w[3]}};
+    return mask16(x, [](unsigned d) { return d != 0u; });
+}
+// j may be a run-time value: every word is indexed by a constant and the one
+// that holds the byte is selected, so the words stay in registers
+__device__ __forceinline__ void set_byte(wf_bytes16& b, int j, unsigned value) {
+    const int sft = (j & 3) * 8, k = j >> 2;
+    const unsigned keep = ~(0xffu << sft), v = value << sft;
+    b.w[0] = k == 0 ? (b.w[0] & keep) | v : b.w[0];
+    b.w[1] = k == 1 ? (b.w[1] & keep) | v : b.w[1];
+    b.w[2] = k == 2 ? (b.w[2] & keep) | v : b.w[2];
+    b.w[3] = k == 3 ? (b.w[3] & keep) | v : b.w[3];
+}
+// one 16-byte store, only if a byte changed (or `always`)
+__device__ __forceinline__ void store16_if_changed(unsigned char* p, const wf_bytes16& now,
+                                                   const wf_bytes16& old, bool always = false) {
+    if (always || now.w[0] != old.w[0] || now.w[1] != old.w[1] || now.w[2] != old.w[2]
+        || now.w[3] != old.w[3])
+        *reinterpret_cast<uint4*>(p) = make_uint4(now.w[0], now.w[1], now.w[2], now.w[3]);
+}
+// OR over the four lanes of a row, the result in all four
+__device__ __forceinline__ unsigned long long quad_or(unsigned long long x) {
+    x |= __shfl_xor(x, 1, WAVE);
+    return x | __shfl_xor(x, 2, WAVE);
+}
+// sum over the wave, the result in every lane
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) x += __shfl_xor(x, d, WAVE);
+    return x;
+}
+// inclusive prefix sum over the wave
+__device__ __forceinline__ int wave_prefix_sum(int x, int lane) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int v = __shfl_up(x, d, WAVE);
+        if (lane >= d) x += v;
+    }
+    return x;
+}
+// Block sums of wave totals: v[k] is wave-uniform on entry and the sum over
+// the block's waves in thread 0 on return (no other thread may use it). It
+// holds the block's barrier, so every thread of the block must get here.
+template <typename T, int N>
+__device__ __forceinline__ void block_sum(T (&v)[N]) {
+    __shared__ T part[N][BLOCK / WAVE];
+    if (threadIdx.x % WAVE == 0)
+        for (int k = 0; k < N; ++k) part[k][threadIdx.x / WAVE] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 0; k < N; ++k) v[k] = part[k][0] + part[k][1] + part[k][2] + part[k][3];
+}
+template <typename T>
+__device__ __forceinline__ T block_sum(T wave_total) {
+    T v[1] = {wave_total};
+    block_sum(v);
+    return v[0];
+}
+// Appends (run, step) for every set bit of a per-lane 64-step mask to a counted
+// list, one bit per lane and pass; entries past cap are counted, not written.
+__device__ __forceinline__ void wave_append_steps(
+    long long mask, int run, int lane, int* runs, int* steps, int* count, int cap) {
+    while (__any(mask != 0)) {
+        int step = -1;
+        if (mask != 0) { step = __ffsll(mask) - 1; mask &= mask - 1; }
+        const int pos = wave_append_slot(step >= 0, count, lane);
+        if (pos >= 0 && pos < cap) { runs[pos] = run; steps[pos] = step; }
+    }
+}
 
 // ---------------------------------------------------------------------------
 // K3: run/step readiness sweep over HBM-resident run state
@@ -646,21 +759,7 @@ __global__ __launch_bounds__(BLOCK) void run_readiness_kernel(
         }
     }
     if (run < NR) ready_mask_out[run] = ready;
-    // compact the dispatch list, one wave-aggregated append per ready step
-    while (true) {
-        const bool has = ready != 0;
-        if (!__any(has)) break;
-        int step = -1;
-        if (has) {
-            step = __ffsll(ready) - 1;
-            ready &= ready - 1;
-        }
-        const int pos = wave_append_slot(step >= 0, dispatch_count, lane);
-        if (pos >= 0 && pos < cap) {
-            dispatch_runs[pos] = run;
-            dispatch_steps[pos] = step;
-        }
-    }
+    wave_append_steps(ready, run, lane, dispatch_runs, dispatch_steps, dispatch_count, cap);
 }
 
 // ---------------------------------------------------------------------------
@@ -741,20 +840,8 @@ __global__ __launch_bounds__(BLOCK) void wf_sweep_kernel(
             }
         }
     }
-    while (true) {   // wave-aggregated appends, one ready step per pass
-        if (!__any(disp != 0)) break;
-        int step = -1;
-        if (disp != 0) { step = __ffsll(disp) - 1; disp &= disp - 1; }
-        const int pos = wave_append_slot(step >= 0, disp_count, lane);
-        if (pos >= 0 && pos < cap) { disp_runs[pos] = run; disp_steps[pos] = step; }
-    }
-    while (true) {
-        if (!__any(appr != 0)) break;
-        int step = -1;
-        if (appr != 0) { step = __ffsll(appr) - 1; appr &= appr - 1; }
-        const int pos = wave_append_slot(step >= 0, appr_count, lane);
-        if (pos >= 0 && pos < acap) { appr_runs[pos] = run; appr_steps[pos] = step; }
-    }
+    wave_append_steps(disp, run, lane, disp_runs, disp_steps, disp_count, cap);
+    wave_append_steps(appr, run, lane, appr_runs, appr_steps, appr_count, acap);
 }
 
 // for_each expansion: one wave per dispatch entry; all-or-nothing child-slot
@@ -952,6 +1039,18 @@ __global__ __launch_bounds__(BLOCK) void wf_apply_dead_kernel(
 // outstanding has lost them (worker crash / dropped result): the remainder
 // is declared TIMEOUT — counted, converted to failed children — so the
 // commit pass retries them with backoff instead of hanging forever.
+// wf_write_off is that rule for one DISPATCHED step, shared with wf_settle: if
+// the step's `out` children are due it clears children_out and calls
+// `lost(out)`, where the caller books them as failed and counts them.
+// `timeout` is called only for a step that has children out.
+template <class Timeout, class Lost>
+__device__ __forceinline__ void wf_write_off(size_t i, int out, int tick, const int* dispatch_tick,
+                                             int* children_out, Timeout timeout, Lost lost) {
+    if (out <= 0 || dispatch_tick[i] > tick - timeout()) return;
+    children_out[i] = 0;
+    lost(out);
+}
+
 __global__ __launch_bounds__(BLOCK) void wf_timeout_scan_kernel(
     const unsigned char* __restrict__ step_state,
     int* __restrict__ children_out,
@@ -964,12 +1063,11 @@ __global__ __launch_bounds__(BLOCK) void wf_timeout_scan_kernel(
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= NRS) return;
     if (step_state[i] != WFS_DISPATCHED) return;
-    const int lost = children_out[i];
-    if (lost <= 0) return;
-    if (dispatch_tick[i] > *tick_p - cutoff) return;
-    children_fail[i] += lost;
-    children_out[i] = 0;
-    atomicAdd(timeout_count, (unsigned long long)lost);
+    wf_write_off(i, children_out[i], *tick_p, dispatch_tick, children_out, [&] { return cutoff; },
+                 [&](int lost) {
+                     children_fail[i] += lost;
+                     atomicAdd(timeout_count, (unsigned long long)lost);
+                 });
 }
 
 // continuous re-admission (config #5 "hold 1M concurrent runs"): terminal
@@ -1019,7 +1117,48 @@ __global__ __launch_bounds__(BLOCK) void wf_readmit_kernel(
 }
 
 // step commit: aggregate children (engine.go:1623-1645) + retry/backoff
-// (computeBackoff :1573-1595, attempts capped by max_retries)
+// (computeBackoff :1573-1595, attempts capped by max_retries).
+// wf_commit_step is the rule for one DISPATCHED step, shared by wf_commit and
+// wf_settle. `out` and `fail` are its children_out and children_fail (after a
+// write-off, if any). It ends in `done(next state, children sent to retry)`;
+// on a retry it has advanced step_attempts, children_todo and next_ready, and
+// the caller owes children_fail = 0 and its retry counter. `load_policy()` is
+// called on the failed-children branch only and gives .max_retries and
+// .backoff(attempt). `done` is a callable, not a return value, so that each
+// branch keeps the direct stores it had in wf_commit.
+template <class LoadPolicy, class Done>
+__device__ __forceinline__ void wf_commit_step(
+    size_t i, int out, int fail, int tick, int* step_attempts, int* children_todo,
+    const int* max_parallel, int* next_ready, LoadPolicy load_policy, Done done) {
+    if (out != 0) {
+        // window slide: with children still in flight, re-open emission as
+        // soon as there is BOTH work left and room (max_parallel window, or
+        // freed child-arena space for the unlimited case); max_parallel is
+        // read only with work left
+        const bool room = children_todo[i] > 0
+                          && (max_parallel[i] == 0 || out < max_parallel[i]);
+        return done(room ? WFS_PENDING : WFS_DISPATCHED, 0);
+    }
+    if (fail > 0) {
+        const auto policy = load_policy();
+        const int att = step_attempts[i];
+        if (att >= policy.max_retries) return done(WFS_FAILED, 0);
+        step_attempts[i] = att + 1;
+        children_todo[i] += fail;                   // only failed children re-run
+        next_ready[i] = tick + policy.backoff(att + 1);
+        return done(WFS_PENDING, fail);
+    }
+    // partial emission resumes, or the step is done
+    done(children_todo[i] > 0 ? WFS_PENDING : WFS_SUCCEEDED, 0);
+}
+
+// wf_commit's policy: backoff min(2^attempt, 16); the shift is capped at 4 so
+// an attempt count past the width of an int cannot wrap the delay
+struct wf_stock_policy {
+    int max_retries;
+    __device__ __forceinline__ int backoff(int attempt) const { return 1 << min(attempt, 4); }
+};
+
 __global__ __launch_bounds__(BLOCK) void wf_commit_kernel(
     unsigned char* __restrict__ step_state,   // [NR*64]
     int* __restrict__ step_attempts,          // [NR*64]
@@ -1036,34 +1175,18 @@ __global__ __launch_bounds__(BLOCK) void wf_commit_kernel(
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= NRS) return;
     if (step_state[i] != WFS_DISPATCHED) return;
-    if (children_out[i] != 0) {
-        // window slide: with children still in flight, re-open emission as
-        // soon as there is BOTH work left and room (max_parallel window, or
-        // freed child-arena space for the unlimited case)
-        if (children_todo[i] > 0 &&
-            (max_parallel[i] == 0 || children_out[i] < max_parallel[i]))
-            step_state[i] = WFS_PENDING;
-        return;
-    }
-    const int fail = children_fail[i];
-    if (fail > 0) {
-        if (step_attempts[i] < max_retries) {
-            step_attempts[i] += 1;
-            children_todo[i] += fail;      // only failed children re-run
-            children_fail[i] = 0;
-            // backoff min(2^attempts, 16): the shift is capped at 4 so an
-            // attempt count past the width of an int cannot wrap the delay
-            next_ready[i] = *tick_p + (1 << min(step_attempts[i], 4));
-            step_state[i] = WFS_PENDING;
-            atomicAdd(retry_count, (unsigned long long)fail);
-        } else {
-            step_state[i] = WFS_FAILED;
-        }
-    } else if (children_todo[i] > 0) {
-        step_state[i] = WFS_PENDING;       // partial emission resumes
-    } else {
-        step_state[i] = WFS_SUCCEEDED;
-    }
+    const int out = children_out[i];
+    const int fail = out != 0 ? 0 : children_fail[i];   // read only where the rule uses it
+    wf_commit_step(
+        i, out, fail, *tick_p, step_attempts, children_todo, max_parallel, next_ready,
+        [&] { return wf_stock_policy{max_retries}; },
+        [&](int next, int retried) {
+            if (next != WFS_DISPATCHED) step_state[i] = (unsigned char)next;
+            if (retried > 0) {
+                children_fail[i] = 0;
+                atomicAdd(retry_count, (unsigned long long)retried);
+            }
+        });
 }
 
 // run status roll-up (updateRunStatus :1647-1699): all steps SUCCEEDED or
@@ -1146,18 +1269,14 @@ __global__ __launch_bounds__(BLOCK) void wf_admit_count_kernel(
     int* __restrict__ blk_scan,                   // [nblk+1] counts, scanned next
     int NR)
 {
-    __shared__ int cnt[BLOCK / WAVE];
     const int run = blockIdx.x * BLOCK + threadIdx.x;
     const int w = threadIdx.x / WAVE;
     const unsigned long long m =
         __ballot(run < NR && run_life[run] == WFL_FREE);
-    if (threadIdx.x % WAVE == 0) {
+    if (threadIdx.x % WAVE == 0)
         free_mask[(size_t)blockIdx.x * (BLOCK / WAVE) + w] = m;
-        cnt[w] = __popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        blk_scan[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    const int free = block_sum((int)__popcll(m));
+    if (threadIdx.x == 0) blk_scan[blockIdx.x] = free;
 }
 
 // admission pass 2: in-place exclusive scan of the block counts by one
@@ -1397,13 +1516,12 @@ __global__ __launch_bounds__(BLOCK) void wf_retire_kernel(
 // writes, and the admission itself is no event. FREE rows cost their life
 // byte only.
 //
-// Layout: 4 lanes per row, 16 steps (one 16-byte load of the states and one
-// of the shadow) per lane, 16 rows per wave, 64 rows per block. A wave with
-// no difference and no generation change leaves after the loads. Otherwise
-// it reserves list space with one atomic for the whole wave (per-lane counts,
-// wave prefix sum); a record at a position >= cap is not written and its
-// shadow byte does not advance, so the next pass finds the change again: a
-// full list delays and coalesces events, it loses none.
+// Row-scan layout (see the helpers above K3), the shadow read like the states.
+// A wave with no difference and no generation change leaves after the loads.
+// Otherwise it reserves list space with one atomic for the whole wave
+// (per-lane counts, wave prefix sum); a record at a position >= cap is not
+// written and its shadow byte does not advance, so the next pass finds the
+// change again: a full list delays and coalesces events, it loses none.
 //
 // ev_count: a wave adds to it only if it read it below cap, and adds at most
 // 1024 (16 rows x 64 steps). Every wave of a pass can do that once, so
@@ -1421,36 +1539,23 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
     int* __restrict__ ev_count,                     // [1]
     int NR, int cap)
 {
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const auto [r, q, off] = wf_row_coords();
     const int lane = threadIdx.x % WAVE;
-    const int r = t >> 2;                           // 4 lanes per row
-    const int q = t & 3;                            // steps 16q .. 16q+15
     const bool live = r < NR && run_life[r] != WFL_FREE;
-    const size_t off = (size_t)r * 64 + (size_t)q * 16;
     int gen = 0;
     bool regen = false;
-    uint4 st = make_uint4(0u, 0u, 0u, 0u), sh = st; // WFS_PENDING == 0
+    wf_bytes16 st = {}, sh = {};                    // WFS_PENDING == 0
     if (live) {
         gen = run_gen[r];
         regen = gen != ev_shadow_gen[r];
-        st = *reinterpret_cast<const uint4*>(step_state + off);
-        if (!regen) sh = *reinterpret_cast<const uint4*>(ev_shadow_state + off);
+        st = load16(step_state + off);
+        if (!regen) sh = load16(ev_shadow_state + off);
     }
-    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
-    const unsigned hw[4] = {sh.x, sh.y, sh.z, sh.w};
-    unsigned diff = 0u;                             // bit j: step 16q+j differs
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        diff |= (unsigned)((((sw[j >> 2] ^ hw[j >> 2]) >> ((j & 3) * 8)) & 0xffu) != 0u) << j;
+    const unsigned diff = differ16(st, sh);         // bit j: step 16q+j differs
     const int n = __popc(diff);
     if (!__any(n > 0 || regen)) return;             // wave-uniform early exit
 
-    int incl = n;                                   // inclusive wave prefix sum
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int v = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_prefix_sum(n, lane);
     const int total = __shfl(incl, WAVE - 1, WAVE);
     int base = 0;
     if (lane == 0 && total > 0) {
@@ -1461,26 +1566,22 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
     base = __shfl(base, 0, WAVE);
     int pos = base + incl - n;
     const int stamp = 2 * *tick_p + phase;
-    unsigned nw[4] = {hw[0], hw[1], hw[2], hw[3]};  // the shadow after this pass
+    wf_bytes16 now = sh;                            // the shadow after this pass
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         if ((diff >> j) & 1u) {
             if (pos < cap) {
-                const int sft = (j & 3) * 8;
-                const unsigned from = (hw[j >> 2] >> sft) & 0xffu;
-                const unsigned to = (sw[j >> 2] >> sft) & 0xffu;
+                const unsigned from = byte16(sh, j), to = byte16(st, j);
                 *reinterpret_cast<int4*>(ev_rec + (size_t)pos * 4) = make_int4(
                     r, gen, (int)((unsigned)(q * 16 + j) | from << 8 | to << 16), stamp);
-                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | (to << sft);
+                set_byte(now, j, to);
             }
             ++pos;
         }
     }
     // a re-admitted row's stale shadow is replaced whole; otherwise the
     // shadow is written only where an event advanced it
-    if (regen || nw[0] != hw[0] || nw[1] != hw[1] || nw[2] != hw[2] || nw[3] != hw[3])
-        *reinterpret_cast<uint4*>(ev_shadow_state + off) =
-            make_uint4(nw[0], nw[1], nw[2], nw[3]);
+    store16_if_changed(ev_shadow_state + off, now, sh, regen);
     if (regen && q == 0) ev_shadow_gen[r] = gen;
 }
 
@@ -1489,9 +1590,10 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
 // ---------------------------------------------------------------------------
 // With a per-step policy the tick launches wf_settle in place of the pair
 // wf_timeout_scan + wf_commit. Both of those act on index i only, so running
-// them back to back per step is the same computation; what differs is where
-// the constants come from. The policy is held per template (templates are
-// append-only), and run_tmpl[r] names the template of the row's occupant:
+// them back to back per step is the same computation, and it is the same
+// code: wf_write_off, then wf_commit_step. The policy is held per template
+// (templates are append-only), and run_tmpl[r] names the template of the
+// row's occupant:
 //   tmpl_policy[(t*64+s)*4 ..] = (max_retries, backoff_ticks, cap_ticks,
 //                                 multiplier_q8), one 16-byte record per step
 //   tmpl_timeout[t*64+s]       = ticks after which outstanding children are
@@ -1501,10 +1603,15 @@ __global__ __launch_bounds__(BLOCK) void wf_journal_kernel(
 // ranges and checks only that the template id is inside the table. A row
 // whose id is not is left alone.
 //
-// One deliberate difference from the pair: FREE rows are skipped. With a step
-// timeout longer than the pipeline cutoff wf_retire can free a row that still
-// holds a DISPATCHED step with children counted outstanding; its bytes belong
-// to nobody and the next admission overwrites them.
+// What still differs from the pair:
+//   - the constants: launch arguments and wf_stock_policy there, the
+//     template's timeout and policy record (wf_step_policy) here;
+//   - FREE rows are skipped. With a step timeout longer than the pipeline
+//     cutoff wf_retire can free a row that still holds a DISPATCHED step with
+//     children counted outstanding; its bytes belong to nobody and the next
+//     admission overwrites them;
+//   - the counters get one add per block, not per step, and children_fail
+//     one store per step, after write-off and retry, not one in each.
 //
 // backoff(k), integers only (16.16 fixed point, multiplier in 8.8); the
 // oracle (reference.wf_backoff_ref) uses the same arithmetic:
@@ -1526,15 +1633,19 @@ __device__ __forceinline__ int wf_backoff_ticks(int k, int backoff_ticks, int ca
     return (int)((d + 65535ull) >> 16);
 }
 
-// Layout as the journal and the hold scan: 4 lanes per row, 16 steps (one
-// 16-byte state load) per lane, 16 rows per wave, 64 rows per block. A FREE
-// row costs its life byte. A wave with no DISPATCHED byte does nothing more
-// after the loads and writes nothing. Only a lane that holds a DISPATCHED
-// byte reads run_tmpl and the counter columns of those steps, and only a step
-// with failed children and none outstanding reads its policy record. A lane
-// owns its 16 state bytes and stores them back, as one 16-byte store, only if
-// one changed. timeout_count / retry_count: summed per block, at most one
-// atomic add per block and counter.
+// one record of tmpl_policy: max_retries, backoff_ticks, cap_ticks, multiplier_q8
+struct wf_step_policy {
+    int max_retries, backoff_ticks, cap_ticks, mult_q8;
+    __device__ __forceinline__ int backoff(int attempt) const {
+        return wf_backoff_ticks(attempt, backoff_ticks, cap_ticks, mult_q8);
+    }
+};
+
+// Row-scan layout (see the helpers above K3). A FREE row costs its life byte.
+// A wave with no DISPATCHED byte does nothing more after the loads and writes
+// nothing. Only a lane that holds a DISPATCHED byte reads run_tmpl and the
+// counter columns of those steps, and only a step with failed children and
+// none outstanding reads its policy record.
 __global__ __launch_bounds__(BLOCK) void wf_settle_kernel(
     unsigned char* __restrict__ step_state,         // [NR*64]
     int* __restrict__ step_attempts,                // [NR*64]
@@ -1553,27 +1664,20 @@ __global__ __launch_bounds__(BLOCK) void wf_settle_kernel(
     unsigned long long* __restrict__ retry_count,
     int NR, int TC)
 {
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
-    const int r = t >> 2;                           // 4 lanes per row
-    const int q = t & 3;                            // steps 16q .. 16q+15
+    const auto [r, q, off] = wf_row_coords();
     const bool live = r < NR && run_life[r] != WFL_FREE;
-    const size_t off = (size_t)r * 64 + (size_t)q * 16;
-    uint4 st = make_uint4(0u, 0u, 0u, 0u);          // WFS_PENDING == 0
-    if (live) st = *reinterpret_cast<const uint4*>(step_state + off);
-    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
-    unsigned disp = 0u;                             // bit j: step 16q+j is DISPATCHED
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        disp |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_DISPATCHED) << j;
+    wf_bytes16 st = {};                             // WFS_PENDING == 0
+    if (live) st = load16(step_state + off);
+    unsigned disp = match16(st, WFS_DISPATCHED);    // bit j: step 16q+j is DISPATCHED
 
-    unsigned long long lost_sum = 0ull, retry_sum = 0ull;
+    unsigned long long sums[2] = {0ull, 0ull};      // children lost, children retried
     if (__any(disp != 0u)) {                        // wave-uniform
         if (disp != 0u) {
             const int tmpl = run_tmpl[r];
             if (tmpl < 0 || tmpl >= TC) disp = 0u;  // no such template: leave the row
             const size_t pol = (size_t)tmpl * 64 + (size_t)q * 16;
             const int tick = *tick_p;
-            unsigned nw[4] = {sw[0], sw[1], sw[2], sw[3]};
+            wf_bytes16 now = st;
 #pragma unroll 1
             for (unsigned f = disp; f != 0u; f &= f - 1u) {
                 const int j = __ffs((int)f) - 1;
@@ -1582,60 +1686,28 @@ __global__ __launch_bounds__(BLOCK) void wf_settle_kernel(
                 int fail = children_fail[i];
                 const int fail0 = fail;
                 // 1. timeout: the remainder is lost and counts as failed
-                if (out > 0 && dispatch_tick[i] <= tick - tmpl_timeout[pol + j]) {
-                    fail += out;
-                    lost_sum += (unsigned long long)out;
-                    out = 0;
-                    children_out[i] = 0;
-                }
+                wf_write_off(i, out, tick, dispatch_tick, children_out,
+                             [&] { return tmpl_timeout[pol + j]; },
+                             [&](int lost) { fail += lost; sums[0] += lost; out = 0; });
                 // 2. commit
                 int next = WFS_DISPATCHED;
-                if (out != 0) {
-                    // window slide: work left and room in the window
-                    const int mp = max_parallel[i];
-                    if (children_todo[i] > 0 && (mp == 0 || out < mp)) next = WFS_PENDING;
-                } else if (fail > 0) {
-                    const int4 p = tmpl_policy[pol + j];  // max_retries, backoff, cap, mult
-                    const int att = step_attempts[i];
-                    if (att < p.x) {
-                        step_attempts[i] = att + 1;
-                        children_todo[i] += fail;   // only failed children re-run
-                        next_ready[i] = tick + wf_backoff_ticks(att + 1, p.y, p.z, p.w);
-                        retry_sum += (unsigned long long)fail;
-                        fail = 0;
-                        next = WFS_PENDING;
-                    } else {
-                        next = WFS_FAILED;
-                    }
-                } else {
-                    next = children_todo[i] > 0 ? WFS_PENDING : WFS_SUCCEEDED;
-                }
+                wf_commit_step(
+                    i, out, fail, tick, step_attempts, children_todo, max_parallel, next_ready,
+                    [&] { const int4 p = tmpl_policy[pol + j];
+                          return wf_step_policy{p.x, p.y, p.z, p.w}; },
+                    [&](int to, int retried) { next = to; sums[1] += retried; fail -= retried; });
                 if (fail != fail0) children_fail[i] = fail;
-                const int sft = (j & 3) * 8;
-                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | ((unsigned)next << sft);
+                set_byte(now, j, (unsigned)next);
             }
-            if (nw[0] != sw[0] || nw[1] != sw[1] || nw[2] != sw[2] || nw[3] != sw[3])
-                *reinterpret_cast<uint4*>(step_state + off) =
-                    make_uint4(nw[0], nw[1], nw[2], nw[3]);
+            store16_if_changed(step_state + off, now, st);
         }
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            lost_sum += __shfl_xor(lost_sum, d, WAVE);
-            retry_sum += __shfl_xor(retry_sum, d, WAVE);
-        }
+        sums[0] = wave_sum(sums[0]);
+        sums[1] = wave_sum(sums[1]);
     }
-    // one add per counter and block, not per wave (see wf_hold_scan)
-    __shared__ unsigned long long part[2][BLOCK / WAVE];
-    if (threadIdx.x % WAVE == 0) {
-        part[0][threadIdx.x / WAVE] = lost_sum;
-        part[1][threadIdx.x / WAVE] = retry_sum;
-    }
-    __syncthreads();
+    block_sum(sums);
     if (threadIdx.x == 0) {
-        const unsigned long long nl = part[0][0] + part[0][1] + part[0][2] + part[0][3];
-        const unsigned long long nr = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        if (nl) atomicAdd(timeout_count, nl);
-        if (nr) atomicAdd(retry_count, nr);
+        if (sums[0]) atomicAdd(timeout_count, sums[0]);
+        if (sums[1]) atomicAdd(retry_count, sums[1]);
     }
 }
 
@@ -1692,13 +1764,12 @@ __device__ __forceinline__ bool wf_cond_value(const int4 rec,
     return v != (((code >> 4) & 1) != 0);
 }
 
-// wf_cond_eval runs directly before wf_sweep. Layout as wf_settle: 4 lanes per
-// row, 16 steps (one 16-byte state load) per lane, 64 rows per block. A row
-// is looked at only if it is LIVE, run_active is set and run_tmpl is inside
-// the table; the four lanes OR their shares of `satisfied` (SUCCEEDED or
-// SKIPPED, as the sweep) and `pending` with two xor-shuffles. A wave in which
-// no row has a PENDING step with a predicate does nothing more and writes
-// nothing. A PENDING predicate step whose deps are satisfied is evaluated:
+// wf_cond_eval runs directly before wf_sweep. Row-scan layout (see the helpers
+// above K3). A row is looked at only if it is LIVE, run_active is set and
+// run_tmpl is inside the table; the four lanes OR their shares of `satisfied`
+// (SUCCEEDED or SKIPPED, as the sweep). A wave in which no row has a PENDING
+// step with a predicate does nothing more and writes nothing. A PENDING
+// predicate step whose deps are satisfied is evaluated:
 //   CONDITION  its bit in cond_bits[run] is set or cleared and step_out is
 //              1 or 0; the sweep of this tick commits it, unchanged
 //   guard      true: the step stays PENDING; false: it becomes SKIPPED
@@ -1708,9 +1779,8 @@ __device__ __forceinline__ bool wf_cond_value(const int4 rec,
 // looked at. Each step is evaluated at most once per launch. next_ready is
 // not consulted: operands are final and inputs constant, so a step that
 // returns to PENDING (retry, for_each window) evaluates the same again.
-// cond_bits[run] is written once per row by lane q == 0; a lane stores its 16
-// state bytes back only if one changed; cond_counts (true, false) gets at
-// most one atomic add per counter and block.
+// cond_bits[run] is written once per row by lane q == 0; cond_counts (true,
+// false) gets at most one atomic add per counter and block.
 __global__ __launch_bounds__(BLOCK) void wf_cond_eval_kernel(
     unsigned char* __restrict__ step_state,         // [NR*64]
     const long long* __restrict__ deps_mask,        // [NR*64]
@@ -1726,45 +1796,30 @@ __global__ __launch_bounds__(BLOCK) void wf_cond_eval_kernel(
     unsigned long long* __restrict__ cond_counts,   // [2] true, false
     int NR, int TC, int IW)
 {
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
-    const int r = t >> 2;                           // 4 lanes per row
-    const int q = t & 3;                            // steps 16q .. 16q+15
-    const size_t off = (size_t)r * 64 + (size_t)q * 16;
+    const auto [r, q, off] = wf_row_coords();
     bool look = r < NR && run_life[r] == WFL_LIVE && run_active[r] != 0;
     int tmpl = 0;
     if (look) {
         tmpl = run_tmpl[r];
         look = tmpl >= 0 && tmpl < TC;
     }
-    uint4 st = make_uint4(0u, 0u, 0u, 0u);
+    wf_bytes16 st = {};
     unsigned long long cmask = 0ull;
     if (look) {
-        st = *reinterpret_cast<const uint4*>(step_state + off);
+        st = load16(step_state + off);
         cmask = tmpl_cond_mask[tmpl];
     }
-    const unsigned sw[4] = {st.x, st.y, st.z, st.w};
-    unsigned nw[4] = {sw[0], sw[1], sw[2], sw[3]};
-    unsigned pend = 0u;                             // bit j: step 16q+j is PENDING
-    if (look) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            pend |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_PENDING) << j;
-    }
+    wf_bytes16 now = st;
+    const unsigned pend = look ? match16(st, WFS_PENDING) : 0u;   // bit j: step 16q+j
     // this lane's PENDING steps that carry a predicate and are not yet decided
     unsigned todo = pend & (unsigned)(cmask >> (q * 16)) & 0xffffu;
     unsigned long long setm = 0ull, clrm = 0ull;
     unsigned n_true = 0u, n_false = 0u;
     bool again = __any(todo != 0u);                 // wave-uniform
     while (again) {
-        unsigned sat16 = 0u;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const unsigned b = (nw[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-            sat16 |= (unsigned)(b == WFS_SUCCEEDED || b == WFS_SKIPPED) << j;
-        }
-        unsigned long long sat = (unsigned long long)sat16 << (q * 16);
-        sat |= __shfl_xor(sat, 1, WAVE);
-        sat |= __shfl_xor(sat, 2, WAVE);
+        const unsigned sat16 = mask16(
+            now, [](unsigned s) { return s == WFS_SUCCEEDED || s == WFS_SKIPPED; });
+        const unsigned long long sat = quad_or((unsigned long long)sat16 << (q * 16));
         bool skipped = false;
 #pragma unroll 1
         for (unsigned f = todo; f != 0u; f &= f - 1u) {
@@ -1782,8 +1837,7 @@ __global__ __launch_bounds__(BLOCK) void wf_cond_eval_kernel(
                 if (v) setm |= bit; else clrm |= bit;
                 step_out[i] = v ? 1 : 0;
             } else if (!v) {
-                const int sft = (j & 3) * 8;
-                nw[j >> 2] = (nw[j >> 2] & ~(0xffu << sft)) | ((unsigned)WFS_SKIPPED << sft);
+                set_byte(now, j, WFS_SKIPPED);
                 skipped = true;
             }
         }
@@ -1792,25 +1846,17 @@ __global__ __launch_bounds__(BLOCK) void wf_cond_eval_kernel(
     }
     unsigned long long acc = 0ull;
     if (__any((setm | clrm) != 0ull || n_true + n_false != 0u)) {   // wave-uniform
-        setm |= __shfl_xor(setm, 1, WAVE);
-        setm |= __shfl_xor(setm, 2, WAVE);
-        clrm |= __shfl_xor(clrm, 1, WAVE);
-        clrm |= __shfl_xor(clrm, 2, WAVE);
+        setm = quad_or(setm);
+        clrm = quad_or(clrm);
         if (q == 0 && (setm | clrm) != 0ull)
             cond_bits[r] = (cond_bits[r] & ~clrm) | setm;
-        if (nw[0] != sw[0] || nw[1] != sw[1] || nw[2] != sw[2] || nw[3] != sw[3])
-            *reinterpret_cast<uint4*>(step_state + off) =
-                make_uint4(nw[0], nw[1], nw[2], nw[3]);
-        // wave totals in one butterfly: two 32-bit fields (each <= 1024)
-        acc = (unsigned long long)n_true | (unsigned long long)n_false << 32;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) acc += __shfl_xor(acc, d, WAVE);
+        store16_if_changed(step_state + off, now, st);
+        // wave totals in one butterfly: two 32-bit fields (each <= 1024 per
+        // wave, <= 4096 per block)
+        acc = wave_sum((unsigned long long)n_true | (unsigned long long)n_false << 32);
     }
-    __shared__ unsigned long long part[BLOCK / WAVE];
-    if (threadIdx.x % WAVE == 0) part[threadIdx.x / WAVE] = acc;
-    __syncthreads();
+    const unsigned long long sum = block_sum(acc);
     if (threadIdx.x == 0) {
-        const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
         const unsigned long long nt = sum & 0xffffffffull, nf = sum >> 32;
         if (nt) atomicAdd(&cond_counts[0], nt);
         if (nf) atomicAdd(&cond_counts[1], nf);
@@ -1868,16 +1914,14 @@ __global__ __launch_bounds__(BLOCK) void wf_child_payload_kernel(
 // otherwise it is empty, whatever the words hold: a slot can be cancelled,
 // drained and re-admitted between two ticks with no pass in between.
 //
-// wf_hold_scan runs inside the tick, directly after wf_sweep. Layout as the
-// journal: 4 lanes per row, 16 steps (one 16-byte state load) per lane, 16
-// rows per wave, 64 rows per block; the four lanes of a row OR their 16 mask
-// bits together with two xor-shuffles and lane q == 0 owns the mask word. A
-// wave with no WAITING byte, no open hold and no generation change does
-// nothing more after the loads and writes nothing; it never touches
-// hold_tick / hold_ttl, which are read only for a hold that continues. The
-// tables after a pass are a pure function of the tables before it; the
-// atomics are the cumulative counters (opened, expired) and the open-hold
-// gauge, at most one add per block each.
+// wf_hold_scan runs inside the tick, directly after wf_sweep. Row-scan layout
+// (see the helpers above K3); the four lanes of a row OR their 16 mask bits
+// together and lane q == 0 owns the mask word. A wave with no WAITING byte,
+// no open hold and no generation change does nothing more after the loads
+// and writes nothing; it never touches hold_tick / hold_ttl, which are read
+// only for a hold that continues. The tables after a pass are a pure
+// function of the tables before it; the atomics are the cumulative counters
+// (opened, expired) and the open-hold gauge, at most one add per block each.
 //
 // A hold opened at tick h with ttl T expires in the pass of tick h + T if it
 // is still WAITING then: the step becomes FAILED, wf_status fails the run
@@ -1897,11 +1941,8 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_scan_kernel(
     int* __restrict__ hold_open,                    // [1]
     int NR)
 {
-    const int t = blockIdx.x * BLOCK + threadIdx.x;
-    const int r = t >> 2;                           // 4 lanes per row
-    const int q = t & 3;                            // steps 16q .. 16q+15
+    const auto [r, q, off] = wf_row_coords();
     const int life = r < NR ? (int)run_life[r] : WFL_FREE;
-    const size_t off = (size_t)r * 64 + (size_t)q * 16;
     bool act = false, match = false;
     int gen = 0;
     unsigned long long raw = 0ull;                  // the mask word as stored
@@ -1914,13 +1955,10 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_scan_kernel(
         // the states of a LIVE row are loaded with the narrow words above,
         // not after the active byte: one dependent round less for the rows
         // that matter, 64 bytes read in vain for a terminal, unreported one
-        uint4 st = make_uint4(0u, 0u, 0u, 0u);
-        if (life == WFL_LIVE) st = *reinterpret_cast<const uint4*>(step_state + off);
+        wf_bytes16 st = {};
+        if (life == WFL_LIVE) st = load16(step_state + off);
         if (act) {
-            const unsigned sw[4] = {st.x, st.y, st.z, st.w};
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                wait |= (unsigned)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu) == WFS_WAITING) << j;
+            wait = match16(st, WFS_WAITING);
             if (wait != 0u) {                       // bytes at s >= n_steps are no steps
                 const int left = (int)n_steps[r] - q * 16;
                 wait &= left >= 16 ? 0xffffu : left <= 0 ? 0u : (1u << left) - 1u;
@@ -1959,9 +1997,7 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_scan_kernel(
     unsigned long long acc = 0ull;
     if (busy) {                                     // wave-uniform
         // the row's new mask: OR of its four lanes' bits (lanes 4k .. 4k+3)
-        unsigned long long now = (unsigned long long)keep << (q * 16);
-        now |= __shfl_xor(now, 1, WAVE);
-        now |= __shfl_xor(now, 2, WAVE);
+        const unsigned long long now = quad_or((unsigned long long)keep << (q * 16));
         int open = 0;
         if (q == 0 && life != WFL_FREE) {
             if (act) {
@@ -1973,19 +2009,11 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_scan_kernel(
             }
         }
         // wave totals in one butterfly: three 21-bit fields (each <= 1024)
-        acc = (unsigned long long)opened | (unsigned long long)expired << 21
-            | (unsigned long long)open << 42;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) acc += __shfl_xor(acc, d, WAVE);
+        acc = wave_sum((unsigned long long)opened | (unsigned long long)expired << 21
+                       | (unsigned long long)open << 42);
     }
-    // one add per counter and block, not per wave: with a hold open in most
-    // rows of a large table every wave has something to add, and adds to one
-    // word are served one after the other
-    __shared__ unsigned long long part[BLOCK / WAVE];
-    if (threadIdx.x % WAVE == 0) part[threadIdx.x / WAVE] = acc;
-    __syncthreads();
+    const unsigned long long sum = block_sum(acc);
     if (threadIdx.x == 0) {
-        const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
         const unsigned long long no = sum & 0x1fffffull, ne = (sum >> 21) & 0x1fffffull;
         const int nopen = (int)(sum >> 42);         // each field <= 4096
         if (no) atomicAdd(&hold_counts[0], no);
@@ -2012,7 +2040,6 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_list_count_kernel(
     int* __restrict__ blk_scan,                     // [nblk+1] counts, scanned next
     int NR)
 {
-    __shared__ int cnt[BLOCK / WAVE];
     const int r = blockIdx.x * BLOCK + threadIdx.x;
     unsigned long long m = 0ull;
     if (r < NR) {
@@ -2022,28 +2049,17 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_list_count_kernel(
         if (key0 + 63 < cursor) m = 0ull;
         else if (key0 < cursor) m &= ~0ull << (int)(cursor - key0);   // shift 1..63
         if (m != 0ull) {
-            const uint4* row = reinterpret_cast<const uint4*>(step_state + (size_t)r * 64);
+            const unsigned char* row = step_state + (size_t)r * 64;
             unsigned long long w = 0ull;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint4 st = row[k];
-                const unsigned sw[4] = {st.x, st.y, st.z, st.w};
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    w |= (unsigned long long)(((sw[j >> 2] >> ((j & 3) * 8)) & 0xffu)
-                                              == WFS_WAITING) << (k * 16 + j);
-            }
+            for (int k = 0; k < 4; ++k)
+                w |= (unsigned long long)match16(load16(row + k * 16), WFS_WAITING) << (k * 16);
             m &= w;
         }
         list_mask[r] = m;
     }
-    int n = __popcll(m);
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) n += __shfl_xor(n, d, WAVE);
-    if (threadIdx.x % WAVE == 0) cnt[threadIdx.x / WAVE] = n;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        blk_scan[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    const int n = block_sum(wave_sum((int)__popcll(m)));
+    if (threadIdx.x == 0) blk_scan[blockIdx.x] = n;
 }
 
 // hold listing, pass 3: the ordered write. Row r's records start at the
@@ -2064,12 +2080,7 @@ __global__ __launch_bounds__(BLOCK) void wf_hold_list_write_kernel(
     const int w = threadIdx.x / WAVE;
     unsigned long long m = r < NR ? list_mask[r] : 0ull;
     const int n = __popcll(m);
-    int incl = n;                                   // inclusive wave prefix sum
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int v = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += v;
-    }
+    const int incl = wave_prefix_sum(n, lane);
     if (lane == WAVE - 1) wsum[w] = incl;
     __syncthreads();
     int pos = blk_scan[blockIdx.x] + incl - n;
@@ -3023,6 +3034,29 @@ static inline hipStream_t cur_stream() {
     return at::hip::getCurrentHIPStream().stream();
 }
 
+// Argument checks of the wf_* bindings; `op` is the binding's name, so every
+// message starts with it. n is NR*64 for per-step tables, NR for per-run ones.
+using wf_tensors = std::initializer_list<torch::Tensor>;
+
+static void wf_check_numel(const char* op, int64_t n, wf_tensors tables) {
+    for (const auto& t : tables) TORCH_CHECK(t.numel() == n, op, ": table sizes disagree");
+}
+static void wf_check_contiguous(const char* op, wf_tensors tables) {
+    for (const auto& t : tables) TORCH_CHECK(t.is_contiguous(), op, ": tables must be contiguous");
+}
+// tables read or written with 16-byte vector accesses; `what` names them
+static void wf_check_aligned16(const char* op, const char* what, wf_tensors tables) {
+    for (const auto& t : tables)
+        TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", what, " must be 16-byte aligned");
+}
+// the kernels index in int; n is the largest index a launch can form (a
+// row-scan grid overshoots NR*64 by less than 1024)
+static void wf_check_fits_int(const char* op, int64_t n) {
+    TORCH_CHECK(n <= (int64_t)INT_MAX, op, ": table too large");
+}
+// grid of a row-scan kernel: 4 lanes per row
+static int wf_row_grid(int64_t NR) { return (int)((NR * 4 + BLOCK - 1) / BLOCK); }
+
 torch::Tensor policy_first_match(
     torch::Tensor rule_any, torch::Tensor rule_all, torch::Tensor rule_secrets,
     torch::Tensor rule_mcp, torch::Tensor rule_mcp_any,
@@ -3879,8 +3913,8 @@ void wf_admit(torch::Tensor req_tmpl, torch::Tensor req_cond, torch::Tensor req_
                 "wf_admit: request/output arrays shorter than the request count");
     TORCH_CHECK(free_mask.numel() >= (int64_t)nblk * (BLOCK / WAVE)
                 && blk_scan.numel() >= nblk + 1, "wf_admit: workspace too small");
-    TORCH_CHECK(step_state.numel() == (int64_t)NR * 64 && run_life.numel() == NR
-                && run_gen.numel() == NR, "wf_admit: table sizes disagree");
+    wf_check_numel("wf_admit", (int64_t)NR * 64, {step_state});
+    wf_check_numel("wf_admit", NR, {run_life, run_gen});
     const int TC = (int)tmpl_nsteps.size(0);
     TORCH_CHECK(tmpl_deps.numel() == (int64_t)TC * 64, "wf_admit: template sizes disagree");
     hipLaunchKernelGGL(wf_admit_count_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
@@ -3921,8 +3955,8 @@ void wf_cancel(torch::Tensor req_slot, torch::Tensor req_gen,
     const int NR = (int)n_steps.size(0);
     TORCH_CHECK(req_gen.size(0) >= n && out_ok.size(0) >= n,
                 "wf_cancel: request/output arrays shorter than the request count");
-    TORCH_CHECK(step_state.numel() == (int64_t)NR * 64 && run_life.numel() == NR
-                && run_gen.numel() == NR, "wf_cancel: table sizes disagree");
+    wf_check_numel("wf_cancel", (int64_t)NR * 64, {step_state});
+    wf_check_numel("wf_cancel", NR, {run_life, run_gen});
     const int blocks = (n + (BLOCK / WAVE) - 1) / (BLOCK / WAVE);
     hipLaunchKernelGGL(wf_cancel_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
         req_slot.data_ptr<int>(), req_gen.data_ptr<int>(), n,
@@ -3944,9 +3978,8 @@ void wf_retire(torch::Tensor run_life, torch::Tensor run_active, torch::Tensor r
     const int cap = (int)done_slot.size(0);
     TORCH_CHECK(done_gen.size(0) >= cap && done_state.size(0) >= cap,
                 "wf_retire: done arrays disagree");
-    TORCH_CHECK(children_out.numel() == (int64_t)NR * 64 && run_life.numel() == NR
-                && dispatch_tick.numel() == (int64_t)NR * 64,
-                "wf_retire: table sizes disagree");
+    wf_check_numel("wf_retire", (int64_t)NR * 64, {children_out, dispatch_tick});
+    wf_check_numel("wf_retire", NR, {run_life});
     const int blocks = (NR + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(wf_retire_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
         run_life.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
@@ -3966,22 +3999,17 @@ void wf_journal(torch::Tensor step_state, torch::Tensor run_life, torch::Tensor 
     const int64_t NR = run_life.numel();
     const int64_t cap = ev_rec.numel() / 4;
     if (NR <= 0) return;
-    TORCH_CHECK(step_state.numel() == NR * 64 && ev_shadow_state.numel() == NR * 64
-                && run_gen.numel() == NR && ev_shadow_gen.numel() == NR,
-                "wf_journal: table sizes disagree");
+    wf_check_numel("wf_journal", NR * 64, {step_state, ev_shadow_state});
+    wf_check_numel("wf_journal", NR, {run_gen, ev_shadow_gen});
     TORCH_CHECK(cap >= 1 && ev_rec.numel() == cap * 4 && ev_count.numel() >= 1
                 && tick.numel() >= 1, "wf_journal: event list needs cap*4 words, cap >= 1");
-    TORCH_CHECK(step_state.is_contiguous() && ev_shadow_state.is_contiguous()
-                && ev_rec.is_contiguous(), "wf_journal: tables must be contiguous");
+    wf_check_contiguous("wf_journal", {step_state, ev_shadow_state, ev_rec});
     // the counter's bound (see the kernel) and the 4-lanes-per-row grid in int
     TORCH_CHECK(cap + 64 * NR + 1024 <= (int64_t)INT_MAX,
                 "wf_journal: cap + 64*NR would let the event counter wrap");
-    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
-                && (uintptr_t)ev_shadow_state.data_ptr<uint8_t>() % 16 == 0
-                && (uintptr_t)ev_rec.data_ptr<int>() % 16 == 0,
-                "wf_journal: states, shadow and records must be 16-byte aligned");
-    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(wf_journal_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+    wf_check_aligned16("wf_journal", "states, shadow and records",
+                       {step_state, ev_shadow_state, ev_rec});
+    hipLaunchKernelGGL(wf_journal_kernel, dim3(wf_row_grid(NR)), dim3(BLOCK), 0, cur_stream(),
         step_state.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
         run_gen.data_ptr<int>(), tick.data_ptr<int>(), (int)phase,
         ev_shadow_state.data_ptr<uint8_t>(), ev_shadow_gen.data_ptr<int>(),
@@ -3997,21 +4025,14 @@ void wf_hold_scan(torch::Tensor step_state, torch::Tensor n_steps, torch::Tensor
 {
     const int64_t NR = run_life.numel();
     if (NR <= 0) return;
-    TORCH_CHECK(step_state.numel() == NR * 64 && hold_ttl.numel() == NR * 64
-                && hold_tick.numel() == NR * 64 && n_steps.numel() == NR
-                && run_active.numel() == NR && run_gen.numel() == NR
-                && hold_mask.numel() == NR && hold_gen.numel() == NR,
-                "wf_hold_scan: table sizes disagree");
+    wf_check_numel("wf_hold_scan", NR * 64, {step_state, hold_ttl, hold_tick});
+    wf_check_numel("wf_hold_scan", NR, {n_steps, run_active, run_gen, hold_mask, hold_gen});
     TORCH_CHECK(hold_counts.numel() >= 4 && hold_open.numel() >= 1 && tick.numel() >= 1,
                 "wf_hold_scan: counters need 4 + 1 words");
-    TORCH_CHECK(step_state.is_contiguous() && hold_ttl.is_contiguous()
-                && hold_tick.is_contiguous() && hold_mask.is_contiguous(),
-                "wf_hold_scan: tables must be contiguous");
-    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_hold_scan: table too large");
-    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0,
-                "wf_hold_scan: states must be 16-byte aligned");
-    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(wf_hold_scan_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+    wf_check_contiguous("wf_hold_scan", {step_state, hold_ttl, hold_tick, hold_mask});
+    wf_check_fits_int("wf_hold_scan", NR * 64 + 1024);
+    wf_check_aligned16("wf_hold_scan", "states", {step_state});
+    hipLaunchKernelGGL(wf_hold_scan_kernel, dim3(wf_row_grid(NR)), dim3(BLOCK), 0, cur_stream(),
         step_state.data_ptr<uint8_t>(), n_steps.data_ptr<uint8_t>(),
         run_life.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
         run_gen.data_ptr<int>(), tick.data_ptr<int>(), hold_ttl.data_ptr<int>(),
@@ -4033,28 +4054,22 @@ void wf_settle(torch::Tensor step_state, torch::Tensor step_attempts,
     const int64_t NR = run_life.numel();
     const int64_t TC = tmpl_timeout.numel() / 64;
     if (NR <= 0) return;
-    TORCH_CHECK(step_state.numel() == NR * 64 && step_attempts.numel() == NR * 64
-                && children_todo.numel() == NR * 64 && children_out.numel() == NR * 64
-                && children_fail.numel() == NR * 64 && max_parallel.numel() == NR * 64
-                && next_ready.numel() == NR * 64 && dispatch_tick.numel() == NR * 64
-                && run_tmpl.numel() == NR, "wf_settle: table sizes disagree");
+    wf_check_numel("wf_settle", NR * 64,
+                   {step_state, step_attempts, children_todo, children_out, children_fail,
+                    max_parallel, next_ready, dispatch_tick});
+    wf_check_numel("wf_settle", NR, {run_tmpl});
     TORCH_CHECK(TC >= 1 && tmpl_timeout.numel() == TC * 64
                 && tmpl_policy.numel() == TC * 64 * 4 && TC * 64 <= (int64_t)INT_MAX,
                 "wf_settle: policy tables need TC*64*4 and TC*64 words, TC >= 1");
     TORCH_CHECK(tick.numel() >= 1 && timeout_count.numel() >= 1 && retry_count.numel() >= 1,
                 "wf_settle: tick and counters need one word each");
-    TORCH_CHECK(step_state.is_contiguous() && step_attempts.is_contiguous()
-                && children_todo.is_contiguous() && children_out.is_contiguous()
-                && children_fail.is_contiguous() && max_parallel.is_contiguous()
-                && next_ready.is_contiguous() && dispatch_tick.is_contiguous()
-                && run_tmpl.is_contiguous() && tmpl_policy.is_contiguous()
-                && tmpl_timeout.is_contiguous(), "wf_settle: tables must be contiguous");
-    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_settle: table too large");
-    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
-                && (uintptr_t)tmpl_policy.data_ptr<int>() % 16 == 0,
-                "wf_settle: states and policy records must be 16-byte aligned");
-    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(wf_settle_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+    wf_check_contiguous("wf_settle",
+                        {step_state, step_attempts, children_todo, children_out, children_fail,
+                         max_parallel, next_ready, dispatch_tick, run_tmpl, tmpl_policy,
+                         tmpl_timeout});
+    wf_check_fits_int("wf_settle", NR * 64 + 1024);
+    wf_check_aligned16("wf_settle", "states and policy records", {step_state, tmpl_policy});
+    hipLaunchKernelGGL(wf_settle_kernel, dim3(wf_row_grid(NR)), dim3(BLOCK), 0, cur_stream(),
         step_state.data_ptr<uint8_t>(), step_attempts.data_ptr<int>(),
         children_todo.data_ptr<int>(), children_out.data_ptr<int>(),
         children_fail.data_ptr<int>(), max_parallel.data_ptr<int>(),
@@ -4078,27 +4093,19 @@ void wf_cond_eval(torch::Tensor step_state, torch::Tensor deps_mask, torch::Tens
     const int64_t TC = tmpl_cond_mask.numel();
     const int64_t IW = input_words;
     if (NR <= 0) return;
-    TORCH_CHECK(step_state.numel() == NR * 64 && deps_mask.numel() == NR * 64
-                && step_kind.numel() == NR * 64 && run_active.numel() == NR
-                && run_tmpl.numel() == NR && step_out.numel() == NR * 64
-                && cond_bits.numel() == NR, "wf_cond_eval: table sizes disagree");
+    wf_check_numel("wf_cond_eval", NR * 64, {step_state, deps_mask, step_kind, step_out});
+    wf_check_numel("wf_cond_eval", NR, {run_active, run_tmpl, cond_bits});
     TORCH_CHECK(IW >= 1 && IW <= 32 && run_input.numel() == NR * IW,
                 "wf_cond_eval: run_input needs NR*input_words words, 1 <= input_words <= 32");
     TORCH_CHECK(TC >= 1 && tmpl_cond.numel() == TC * 64 * 4 && TC * 64 <= (int64_t)INT_MAX,
                 "wf_cond_eval: predicate tables need TC*64*4 and TC words, TC >= 1");
     TORCH_CHECK(cond_counts.numel() >= 2, "wf_cond_eval: counters need two words");
-    TORCH_CHECK(step_state.is_contiguous() && deps_mask.is_contiguous()
-                && step_kind.is_contiguous() && run_life.is_contiguous()
-                && run_active.is_contiguous() && run_tmpl.is_contiguous()
-                && tmpl_cond.is_contiguous() && tmpl_cond_mask.is_contiguous()
-                && run_input.is_contiguous() && step_out.is_contiguous()
-                && cond_bits.is_contiguous(), "wf_cond_eval: tables must be contiguous");
-    TORCH_CHECK(NR * 64 + 1024 <= (int64_t)INT_MAX, "wf_cond_eval: table too large");
-    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
-                && (uintptr_t)tmpl_cond.data_ptr<int>() % 16 == 0,
-                "wf_cond_eval: states and predicate records must be 16-byte aligned");
-    const int blocks = (int)((NR * 4 + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(wf_cond_eval_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+    wf_check_contiguous("wf_cond_eval",
+                        {step_state, deps_mask, step_kind, run_life, run_active, run_tmpl,
+                         tmpl_cond, tmpl_cond_mask, run_input, step_out, cond_bits});
+    wf_check_fits_int("wf_cond_eval", NR * 64 + 1024);
+    wf_check_aligned16("wf_cond_eval", "states and predicate records", {step_state, tmpl_cond});
+    hipLaunchKernelGGL(wf_cond_eval_kernel, dim3(wf_row_grid(NR)), dim3(BLOCK), 0, cur_stream(),
         step_state.data_ptr<uint8_t>(), (const long long*)deps_mask.data_ptr<int64_t>(),
         step_kind.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
         run_active.data_ptr<uint8_t>(), run_tmpl.data_ptr<int>(),
@@ -4125,9 +4132,7 @@ void wf_child_payload(torch::Tensor child_tag, torch::Tensor child_seq,
                 && run_input.numel() >= IW, "wf_child_payload: table sizes disagree");
     TORCH_CHECK(CB * W <= (int64_t)INT_MAX && run_input.numel() <= (int64_t)INT_MAX,
                 "wf_child_payload: arena too large");
-    TORCH_CHECK(child_tag.is_contiguous() && child_seq.is_contiguous()
-                && run_input.is_contiguous() && child_payload.is_contiguous(),
-                "wf_child_payload: tables must be contiguous");
+    wf_check_contiguous("wf_child_payload", {child_tag, child_seq, run_input, child_payload});
     const int64_t NR = run_input.numel() / IW;
     // 4 rows per block and pass; 2048 blocks fill the device at 8 waves/SIMD
     const int blocks = (int)std::min<int64_t>((CB + BLOCK / WAVE - 1) / (BLOCK / WAVE), 2048);
@@ -4148,12 +4153,9 @@ void wf_apply_out(torch::Tensor send_slots, torch::Tensor send_cnt, torch::Tenso
     const int n = (int)(world * cap);
     TORCH_CHECK(send_slots.numel() >= n && sums_back.numel() >= n && send_cnt.numel() >= world,
                 "wf_apply_out: send tables need world*cap entries");
-    TORCH_CHECK(step_out.numel() == children_done.numel()
-                && children_fail.numel() == children_done.numel()
-                && children_out.numel() == children_done.numel(),
-                "wf_apply_out: table sizes disagree");
-    TORCH_CHECK(sums_back.is_contiguous() && step_out.is_contiguous(),
-                "wf_apply_out: tables must be contiguous");
+    wf_check_numel("wf_apply_out", children_done.numel(),
+                   {step_out, children_fail, children_out});
+    wf_check_contiguous("wf_apply_out", {sums_back, step_out});
     const int blocks = (n + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(wf_apply_out_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
         send_slots.data_ptr<int>(), send_cnt.data_ptr<int>(), child_tag.data_ptr<int>(),
@@ -4176,20 +4178,15 @@ void wf_hold_list(torch::Tensor step_state, torch::Tensor run_life, torch::Tenso
     if (NR <= 0) return;
     const int nblk = (int)((NR + BLOCK - 1) / BLOCK);
     const int64_t cap = (list.numel() - 4) / 4;
-    TORCH_CHECK(step_state.numel() == NR * 64 && hold_tick.numel() == NR * 64
-                && run_active.numel() == NR && run_gen.numel() == NR
-                && hold_mask.numel() == NR && hold_gen.numel() == NR,
-                "wf_hold_list: table sizes disagree");
+    wf_check_numel("wf_hold_list", NR * 64, {step_state, hold_tick});
+    wf_check_numel("wf_hold_list", NR, {run_active, run_gen, hold_mask, hold_gen});
     TORCH_CHECK(list_mask.numel() >= NR && blk_scan.numel() >= nblk + 1,
                 "wf_hold_list: workspace too small");
     TORCH_CHECK(cap >= 1 && list.numel() == 4 + cap * 4 && cap <= (int64_t)INT_MAX,
                 "wf_hold_list: the list needs 4 + cap*4 words, cap >= 1");
-    TORCH_CHECK(step_state.is_contiguous() && list.is_contiguous()
-                && hold_tick.is_contiguous(), "wf_hold_list: tables must be contiguous");
-    TORCH_CHECK(NR * 64 <= (int64_t)INT_MAX, "wf_hold_list: table too large");
-    TORCH_CHECK((uintptr_t)step_state.data_ptr<uint8_t>() % 16 == 0
-                && (uintptr_t)list.data_ptr<int>() % 16 == 0,
-                "wf_hold_list: states and list must be 16-byte aligned");
+    wf_check_contiguous("wf_hold_list", {step_state, list, hold_tick});
+    wf_check_fits_int("wf_hold_list", NR * 64);     // one thread per row: no overshoot
+    wf_check_aligned16("wf_hold_list", "states and list", {step_state, list});
     hipLaunchKernelGGL(wf_hold_list_count_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
         step_state.data_ptr<uint8_t>(), run_life.data_ptr<uint8_t>(),
         run_active.data_ptr<uint8_t>(), run_gen.data_ptr<int>(),
@@ -4216,10 +4213,9 @@ void wf_decide(torch::Tensor req_slot, torch::Tensor req_gen, torch::Tensor req_
     TORCH_CHECK(req_gen.size(0) >= n && req_step.size(0) >= n && req_verdict.size(0) >= n
                 && out_code.size(0) >= n,
                 "wf_decide: request/output arrays shorter than the request count");
-    TORCH_CHECK(step_state.numel() == NR * 64 && step_kind.numel() == NR * 64
-                && run_life.numel() == NR && run_gen.numel() == NR
-                && run_active.numel() == NR && hold_counts.numel() >= 4,
-                "wf_decide: table sizes disagree");
+    wf_check_numel("wf_decide", NR * 64, {step_state, step_kind});
+    wf_check_numel("wf_decide", NR, {run_life, run_gen, run_active});
+    TORCH_CHECK(hold_counts.numel() >= 4, "wf_decide: table sizes disagree");
     const int blocks = (n + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(wf_decide_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
         req_slot.data_ptr<int>(), req_gen.data_ptr<int>(), req_step.data_ptr<int>(),
