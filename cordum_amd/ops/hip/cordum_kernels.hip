@@ -1302,25 +1302,47 @@ __global__ __launch_bounds__(BLOCK) void wf_admit_scan_kernel(
     for (int j = lo; j < hi; ++j) { const int v = blk_scan[j]; blk_scan[j] = run; run += v; }
 }
 
-// admission pass 3: one wave per request. Request i takes the i-th lowest
-// FREE slot (binary search over the scanned block counts, then popcounts
-// over the block's four masks), a pure function of the tables and the
-// request order. Its 64 lanes write the 64-step row, one lane per step, so
-// every table write is one coalesced 64-lane store.
-__global__ __launch_bounds__(BLOCK) void wf_admit_kernel(
-    const int* __restrict__ req_tmpl,             // [n] template id
-    const long long* __restrict__ req_cond,       // [n] condition bits
-    const int* __restrict__ req_fanout,           // [n] FOR_EACH override (0 = none)
-    int n,
-    const long long* __restrict__ tmpl_deps,      // [TC*64]
-    const unsigned char* __restrict__ tmpl_kind,  // [TC*64]
-    const int* __restrict__ tmpl_todo,            // [TC*64]
-    const int* __restrict__ tmpl_maxp,            // [TC*64]
-    const int* __restrict__ tmpl_delay,           // [TC*64]
-    const unsigned char* __restrict__ tmpl_nsteps,// [TC]
-    int TC,
-    const unsigned long long* __restrict__ free_mask,
-    const int* __restrict__ blk_scan, int nblk,
+// the i-th lowest FREE slot of the snapshot (i below the free total), or -1:
+// binary search over the scanned block counts, then popcounts over the
+// block's four masks. Wave-uniform.
+__device__ __forceinline__ int wf_admit_place(
+    int i, int lane, const unsigned long long* __restrict__ free_mask,
+    const int* __restrict__ blk_scan, int nblk, int NR)
+{
+    // largest block b with blk_scan[b] <= i (empty blocks share a prefix)
+    int lo = 0, hi = nblk - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk_scan[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    int k = i - blk_scan[lo];
+    int g = 0;
+    unsigned long long m = free_mask[(size_t)lo * 4];
+    while (g < 3 && k >= __popcll(m)) {
+        k -= __popcll(m);
+        ++g;
+        m = free_mask[(size_t)lo * 4 + g];
+    }
+    // the k-th set bit of m: the one lane whose bit is set with k below it
+    const unsigned long long pick = __ballot(
+        ((m >> lane) & 1ull) && __popcll(m & ((1ull << lane) - 1ull)) == k);
+    const int slot = lo * BLOCK + g * WAVE + (__ffsll((long long)pick) - 1);
+    return (pick == 0ull || slot >= NR) ? -1 : slot;   // -1 cannot happen: masks and scan agree
+}
+
+// the row of an admitted run, by its wave: lane s writes step s of `slot`
+// from template `tid` (steps at and past the template's n_steps are zero),
+// lane 0 the run columns and the handle. `state` is the lane's step state:
+// the one entry that differs between a fresh admission and one with kept steps.
+__device__ __forceinline__ void wf_admit_row(
+    int i, int lane, int slot, int tid, int ns, unsigned char state,
+    const long long* __restrict__ req_cond,
+    const int* __restrict__ req_fanout,
+    const long long* __restrict__ tmpl_deps,
+    const unsigned char* __restrict__ tmpl_kind,
+    const int* __restrict__ tmpl_todo,
+    const int* __restrict__ tmpl_maxp,
+    const int* __restrict__ tmpl_delay,
     unsigned char* __restrict__ step_state,
     int* __restrict__ step_attempts,
     long long* __restrict__ deps_mask,
@@ -1340,54 +1362,16 @@ __global__ __launch_bounds__(BLOCK) void wf_admit_kernel(
     unsigned char* __restrict__ run_life,
     int* __restrict__ run_gen,
     const int* __restrict__ tick_p,
-    int* __restrict__ out_slot,                   // [n]
-    int* __restrict__ out_gen,                    // [n]
-    unsigned long long* __restrict__ admit_count,
-    int NR)
+    int* __restrict__ out_slot,
+    int* __restrict__ out_gen)
 {
-    const int i = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
-    const int lane = threadIdx.x % WAVE;
-    if (i >= n) return;                           // wave-uniform
-    const int total = blk_scan[nblk];
-    if (i == 0 && lane == 0)
-        atomicAdd(admit_count, (unsigned long long)min(n, total));
-    if (i >= total) {                             // table full
-        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
-        return;
-    }
-    // largest block b with blk_scan[b] <= i (empty blocks share a prefix)
-    int lo = 0, hi = nblk - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (blk_scan[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    int k = i - blk_scan[lo];
-    int g = 0;
-    unsigned long long m = free_mask[(size_t)lo * 4];
-    while (g < 3 && k >= __popcll(m)) {
-        k -= __popcll(m);
-        ++g;
-        m = free_mask[(size_t)lo * 4 + g];
-    }
-    // the k-th set bit of m: the one lane whose bit is set with k below it
-    const unsigned long long pick = __ballot(
-        ((m >> lane) & 1ull) && __popcll(m & ((1ull << lane) - 1ull)) == k);
-    const int slot = lo * BLOCK + g * WAVE + (__ffsll((long long)pick) - 1);
-    if (pick == 0ull || slot >= NR) {             // cannot happen: masks and scan agree
-        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
-        return;
-    }
-
-    const int tid = req_tmpl[i];
-    const bool known = tid >= 0 && tid < TC;      // host rejects the rest
-    const int ns = known ? (int)tmpl_nsteps[tid] : 0;
     const int tick1 = *tick_p + 1;                // the run's first tick
     const bool in = lane < ns;
-    const size_t ti = (size_t)(known ? tid : 0) * 64 + lane;
+    const size_t ti = (size_t)tid * 64 + lane;
     const size_t ri = (size_t)slot * 64 + lane;
     const int kind = in ? (int)tmpl_kind[ti] : 0;
     const int fan = req_fanout[i];
-    step_state[ri] = WFS_PENDING;
+    step_state[ri] = state;
     step_attempts[ri] = 0;
     deps_mask[ri] = in ? tmpl_deps[ti] : 0ll;
     step_kind[ri] = (unsigned char)kind;
@@ -1410,6 +1394,116 @@ __global__ __launch_bounds__(BLOCK) void wf_admit_kernel(
         out_slot[i] = slot;
         out_gen[i] = gen;
     }
+}
+
+#define WF_ADMIT_PARAMS \
+    const int* __restrict__ req_tmpl,             /* [n] template id */ \
+    const long long* __restrict__ req_cond,       /* [n] condition bits */ \
+    const int* __restrict__ req_fanout,           /* [n] FOR_EACH override (0 = none) */ \
+    int n, \
+    const long long* __restrict__ tmpl_deps,      /* [TC*64] */ \
+    const unsigned char* __restrict__ tmpl_kind,  /* [TC*64] */ \
+    const int* __restrict__ tmpl_todo,            /* [TC*64] */ \
+    const int* __restrict__ tmpl_maxp,            /* [TC*64] */ \
+    const int* __restrict__ tmpl_delay,           /* [TC*64] */ \
+    const unsigned char* __restrict__ tmpl_nsteps,/* [TC] */ \
+    int TC, \
+    const unsigned long long* __restrict__ free_mask, \
+    const int* __restrict__ blk_scan, int nblk, \
+    unsigned char* __restrict__ step_state, \
+    int* __restrict__ step_attempts, \
+    long long* __restrict__ deps_mask, \
+    unsigned char* __restrict__ step_kind, \
+    int* __restrict__ children_todo, \
+    int* __restrict__ max_parallel, \
+    int* __restrict__ children_out, \
+    int* __restrict__ children_done, \
+    int* __restrict__ children_fail, \
+    int* __restrict__ children_emitted, \
+    int* __restrict__ next_ready, \
+    int* __restrict__ dispatch_tick, \
+    unsigned char* __restrict__ n_steps, \
+    long long* __restrict__ cond_bits, \
+    unsigned char* __restrict__ run_state, \
+    unsigned char* __restrict__ run_active, \
+    unsigned char* __restrict__ run_life, \
+    int* __restrict__ run_gen, \
+    const int* __restrict__ tick_p, \
+    int* __restrict__ out_slot,                   /* [n] */ \
+    int* __restrict__ out_gen,                    /* [n] */ \
+    unsigned long long* __restrict__ admit_count, \
+    int NR
+#define WF_ADMIT_ROW_ARGS \
+    req_cond, req_fanout, tmpl_deps, tmpl_kind, tmpl_todo, tmpl_maxp, tmpl_delay, \
+    step_state, step_attempts, deps_mask, step_kind, children_todo, max_parallel, \
+    children_out, children_done, children_fail, children_emitted, next_ready, \
+    dispatch_tick, n_steps, cond_bits, run_state, run_active, run_life, run_gen, \
+    tick_p, out_slot, out_gen
+
+// admission pass 3: one wave per request. Request i takes the i-th lowest
+// FREE slot, a pure function of the tables and the request order. Its 64
+// lanes write the 64-step row, one lane per step, so every table write is
+// one coalesced 64-lane store.
+__global__ __launch_bounds__(BLOCK) void wf_admit_kernel(WF_ADMIT_PARAMS)
+{
+    const int i = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    if (i >= n) return;                           // wave-uniform
+    const int total = blk_scan[nblk];
+    if (i == 0 && lane == 0)
+        atomicAdd(admit_count, (unsigned long long)min(n, total));
+    const int slot = i < total ? wf_admit_place(i, lane, free_mask, blk_scan, nblk, NR) : -1;
+    if (slot < 0) {                               // table full
+        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
+        return;
+    }
+    const int tid = req_tmpl[i];
+    const bool known = tid >= 0 && tid < TC;      // host rejects the rest
+    const int ns = known ? (int)tmpl_nsteps[tid] : 0;
+    wf_admit_row(i, lane, slot, known ? tid : 0, ns, WFS_PENDING, WF_ADMIT_ROW_ARGS);
+}
+
+// admission with kept steps (rerun from a step): wf_admit_kernel's placement
+// and row, with the steps named by req_keep already done: SKIPPED where
+// req_skip names them too, SUCCEEDED otherwise. The kept set has to lie
+// inside the template's steps and be closed under its dependencies; a request
+// that is not gets -2 and writes nothing else. That is decided first, from
+// the request and the template alone, so -2 wins over a full table, and the
+// i-th free slot of such a request i stays FREE: valid requests land where
+// their index puts them, whatever their neighbours are.
+__global__ __launch_bounds__(BLOCK) void wf_admit_keep_kernel(
+    WF_ADMIT_PARAMS,
+    const long long* __restrict__ req_keep,       // [n] bit s: step s is done
+    const long long* __restrict__ req_skip)       // [n] bit s: ... as SKIPPED
+{
+    const int i = (blockIdx.x * BLOCK + threadIdx.x) / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    if (i >= n) return;                           // wave-uniform
+    const int req = req_tmpl[i];
+    const bool known = req >= 0 && req < TC;      // host rejects the rest
+    const int tid = known ? req : 0;
+    const int ns = known ? (int)tmpl_nsteps[tid] : 0;
+    const unsigned long long keep = (unsigned long long)req_keep[i];
+    const unsigned long long skip = (unsigned long long)req_skip[i] & keep;
+    const bool kept = (keep >> lane) & 1ull;
+    // a 64-step template has no bit past its steps: never shift by 64
+    const bool past = ns < 64 && (keep >> ns) != 0ull;
+    const bool open = kept && lane < ns
+        && ((unsigned long long)tmpl_deps[(size_t)tid * 64 + lane] & ~keep) != 0ull;
+    if (past || __ballot(open) != 0ull) {         // wave-uniform
+        if (lane == 0) { out_slot[i] = -2; out_gen[i] = 0; }
+        return;
+    }
+    const int total = blk_scan[nblk];
+    const int slot = i < total ? wf_admit_place(i, lane, free_mask, blk_scan, nblk, NR) : -1;
+    if (slot < 0) {                               // table full
+        if (lane == 0) { out_slot[i] = -1; out_gen[i] = 0; }
+        return;
+    }
+    if (lane == 0) atomicAdd(admit_count, 1ull);  // a count, not a placement
+    const unsigned char state = !kept ? WFS_PENDING
+        : ((skip >> lane) & 1ull) ? WFS_SKIPPED : WFS_SUCCEEDED;
+    wf_admit_row(i, lane, slot, tid, ns, state, WF_ADMIT_ROW_ARGS);
 }
 
 // cancellation: one wave per request (distinct slots), one lane per step.
@@ -3889,59 +3983,105 @@ void wf_grant(torch::Tensor grant_runs, torch::Tensor grant_steps, torch::Tensor
 // three launches on the current stream: free-slot masks + block counts, the
 // scan of the counts, then one wave per request. free_mask / blk_scan are
 // caller-owned workspaces ([nblk*4] int64, [nblk+1] int32, nblk = ceil(NR/256))
-void wf_admit(torch::Tensor req_tmpl, torch::Tensor req_cond, torch::Tensor req_fanout,
-              torch::Tensor tmpl_deps, torch::Tensor tmpl_kind, torch::Tensor tmpl_todo,
-              torch::Tensor tmpl_maxp, torch::Tensor tmpl_delay, torch::Tensor tmpl_nsteps,
-              torch::Tensor step_state, torch::Tensor step_attempts,
-              torch::Tensor deps_mask, torch::Tensor step_kind,
-              torch::Tensor children_todo, torch::Tensor max_parallel,
-              torch::Tensor children_out, torch::Tensor children_done,
-              torch::Tensor children_fail, torch::Tensor children_emitted,
-              torch::Tensor next_ready, torch::Tensor dispatch_tick,
-              torch::Tensor n_steps, torch::Tensor cond_bits,
-              torch::Tensor run_state, torch::Tensor run_active,
-              torch::Tensor run_life, torch::Tensor run_gen, torch::Tensor tick,
-              torch::Tensor free_mask, torch::Tensor blk_scan,
-              torch::Tensor out_slot, torch::Tensor out_gen, torch::Tensor admit_count)
+#define WF_ADMIT_TENSORS \
+    torch::Tensor req_tmpl, torch::Tensor req_cond, torch::Tensor req_fanout, \
+    torch::Tensor tmpl_deps, torch::Tensor tmpl_kind, torch::Tensor tmpl_todo, \
+    torch::Tensor tmpl_maxp, torch::Tensor tmpl_delay, torch::Tensor tmpl_nsteps, \
+    torch::Tensor step_state, torch::Tensor step_attempts, \
+    torch::Tensor deps_mask, torch::Tensor step_kind, \
+    torch::Tensor children_todo, torch::Tensor max_parallel, \
+    torch::Tensor children_out, torch::Tensor children_done, \
+    torch::Tensor children_fail, torch::Tensor children_emitted, \
+    torch::Tensor next_ready, torch::Tensor dispatch_tick, \
+    torch::Tensor n_steps, torch::Tensor cond_bits, \
+    torch::Tensor run_state, torch::Tensor run_active, \
+    torch::Tensor run_life, torch::Tensor run_gen, torch::Tensor tick, \
+    torch::Tensor free_mask, torch::Tensor blk_scan, \
+    torch::Tensor out_slot, torch::Tensor out_gen, torch::Tensor admit_count
+#define WF_ADMIT_TENSOR_ARGS \
+    req_tmpl, req_cond, req_fanout, tmpl_deps, tmpl_kind, tmpl_todo, tmpl_maxp, \
+    tmpl_delay, tmpl_nsteps, step_state, step_attempts, deps_mask, step_kind, \
+    children_todo, max_parallel, children_out, children_done, children_fail, \
+    children_emitted, next_ready, dispatch_tick, n_steps, cond_bits, run_state, \
+    run_active, run_life, run_gen, tick, free_mask, blk_scan, out_slot, out_gen, \
+    admit_count
+// the kernel arguments both admission kernels take, from the tensors above
+#define WF_ADMIT_KERNEL_ARGS \
+    req_tmpl.data_ptr<int>(), (const long long*)req_cond.data_ptr<int64_t>(), \
+    req_fanout.data_ptr<int>(), n, \
+    (const long long*)tmpl_deps.data_ptr<int64_t>(), tmpl_kind.data_ptr<uint8_t>(), \
+    tmpl_todo.data_ptr<int>(), tmpl_maxp.data_ptr<int>(), tmpl_delay.data_ptr<int>(), \
+    tmpl_nsteps.data_ptr<uint8_t>(), TC, \
+    (const unsigned long long*)free_mask.data_ptr<int64_t>(), \
+    blk_scan.data_ptr<int>(), nblk, \
+    step_state.data_ptr<uint8_t>(), step_attempts.data_ptr<int>(), \
+    (long long*)deps_mask.data_ptr<int64_t>(), step_kind.data_ptr<uint8_t>(), \
+    children_todo.data_ptr<int>(), max_parallel.data_ptr<int>(), \
+    children_out.data_ptr<int>(), children_done.data_ptr<int>(), \
+    children_fail.data_ptr<int>(), children_emitted.data_ptr<int>(), \
+    next_ready.data_ptr<int>(), dispatch_tick.data_ptr<int>(), \
+    n_steps.data_ptr<uint8_t>(), (long long*)cond_bits.data_ptr<int64_t>(), \
+    run_state.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(), \
+    run_life.data_ptr<uint8_t>(), run_gen.data_ptr<int>(), tick.data_ptr<int>(), \
+    out_slot.data_ptr<int>(), out_gen.data_ptr<int>(), \
+    (unsigned long long*)admit_count.data_ptr<int64_t>(), NR
+
+// the checks and the two snapshot launches of an admission; `keep` and
+// `skip` are null for wf_admit. Returns the request count (0: nothing to do).
+static int wf_admit_prepare(const char* op, WF_ADMIT_TENSORS,
+                            const torch::Tensor* keep, const torch::Tensor* skip)
 {
     const int n = (int)req_tmpl.size(0);
-    if (n <= 0) return;
+    if (n <= 0) return 0;
     const int NR = (int)n_steps.size(0);
     const int nblk = (NR + BLOCK - 1) / BLOCK;
     TORCH_CHECK(req_cond.size(0) >= n && req_fanout.size(0) >= n
-                && out_slot.size(0) >= n && out_gen.size(0) >= n,
-                "wf_admit: request/output arrays shorter than the request count");
+                && out_slot.size(0) >= n && out_gen.size(0) >= n
+                && (!keep || (keep->size(0) >= n && skip->size(0) >= n)),
+                op, ": request/output arrays shorter than the request count");
     TORCH_CHECK(free_mask.numel() >= (int64_t)nblk * (BLOCK / WAVE)
-                && blk_scan.numel() >= nblk + 1, "wf_admit: workspace too small");
-    wf_check_numel("wf_admit", (int64_t)NR * 64, {step_state});
-    wf_check_numel("wf_admit", NR, {run_life, run_gen});
+                && blk_scan.numel() >= nblk + 1, op, ": workspace too small");
+    wf_check_numel(op, (int64_t)NR * 64, {step_state});
+    wf_check_numel(op, NR, {run_life, run_gen});
     const int TC = (int)tmpl_nsteps.size(0);
-    TORCH_CHECK(tmpl_deps.numel() == (int64_t)TC * 64, "wf_admit: template sizes disagree");
+    TORCH_CHECK(tmpl_deps.numel() == (int64_t)TC * 64, op, ": template sizes disagree");
+    if (keep) {
+        TORCH_CHECK(keep->scalar_type() == torch::kInt64 && skip->scalar_type() == torch::kInt64,
+                    op, ": the keep and skip masks must be int64");
+        wf_check_contiguous(op, {*keep, *skip});
+    }
     hipLaunchKernelGGL(wf_admit_count_kernel, dim3(nblk), dim3(BLOCK), 0, cur_stream(),
         run_life.data_ptr<uint8_t>(),
         (unsigned long long*)free_mask.data_ptr<int64_t>(), blk_scan.data_ptr<int>(), NR);
     hipLaunchKernelGGL(wf_admit_scan_kernel, dim3(1), dim3(BLOCK), 0, cur_stream(),
         blk_scan.data_ptr<int>(), nblk);
+    return n;
+}
+
+void wf_admit(WF_ADMIT_TENSORS)
+{
+    const int n = wf_admit_prepare("wf_admit", WF_ADMIT_TENSOR_ARGS, nullptr, nullptr);
+    if (n <= 0) return;
+    const int NR = (int)n_steps.size(0), TC = (int)tmpl_nsteps.size(0);
+    const int nblk = (NR + BLOCK - 1) / BLOCK;
     const int blocks = (n + (BLOCK / WAVE) - 1) / (BLOCK / WAVE);
     hipLaunchKernelGGL(wf_admit_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
-        req_tmpl.data_ptr<int>(), (const long long*)req_cond.data_ptr<int64_t>(),
-        req_fanout.data_ptr<int>(), n,
-        (const long long*)tmpl_deps.data_ptr<int64_t>(), tmpl_kind.data_ptr<uint8_t>(),
-        tmpl_todo.data_ptr<int>(), tmpl_maxp.data_ptr<int>(), tmpl_delay.data_ptr<int>(),
-        tmpl_nsteps.data_ptr<uint8_t>(), TC,
-        (const unsigned long long*)free_mask.data_ptr<int64_t>(),
-        blk_scan.data_ptr<int>(), nblk,
-        step_state.data_ptr<uint8_t>(), step_attempts.data_ptr<int>(),
-        (long long*)deps_mask.data_ptr<int64_t>(), step_kind.data_ptr<uint8_t>(),
-        children_todo.data_ptr<int>(), max_parallel.data_ptr<int>(),
-        children_out.data_ptr<int>(), children_done.data_ptr<int>(),
-        children_fail.data_ptr<int>(), children_emitted.data_ptr<int>(),
-        next_ready.data_ptr<int>(), dispatch_tick.data_ptr<int>(),
-        n_steps.data_ptr<uint8_t>(), (long long*)cond_bits.data_ptr<int64_t>(),
-        run_state.data_ptr<uint8_t>(), run_active.data_ptr<uint8_t>(),
-        run_life.data_ptr<uint8_t>(), run_gen.data_ptr<int>(), tick.data_ptr<int>(),
-        out_slot.data_ptr<int>(), out_gen.data_ptr<int>(),
-        (unsigned long long*)admit_count.data_ptr<int64_t>(), NR);
+        WF_ADMIT_KERNEL_ARGS);
+}
+
+// wf_admit with kept steps: the same three launches, the last one the kernel
+// that validates and presets the steps named by req_keep / req_skip ([n] int64)
+void wf_admit_keep(WF_ADMIT_TENSORS, torch::Tensor req_keep, torch::Tensor req_skip)
+{
+    const int n = wf_admit_prepare("wf_admit_keep", WF_ADMIT_TENSOR_ARGS, &req_keep, &req_skip);
+    if (n <= 0) return;
+    const int NR = (int)n_steps.size(0), TC = (int)tmpl_nsteps.size(0);
+    const int nblk = (NR + BLOCK - 1) / BLOCK;
+    const int blocks = (n + (BLOCK / WAVE) - 1) / (BLOCK / WAVE);
+    hipLaunchKernelGGL(wf_admit_keep_kernel, dim3(blocks), dim3(BLOCK), 0, cur_stream(),
+        WF_ADMIT_KERNEL_ARGS,
+        (const long long*)req_keep.data_ptr<int64_t>(),
+        (const long long*)req_skip.data_ptr<int64_t>());
 }
 
 void wf_cancel(torch::Tensor req_slot, torch::Tensor req_gen,
@@ -4586,6 +4726,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wf_status", &wf_status, "K3-WF run status roll-up");
     m.def("wf_grant", &wf_grant, "K3-WF host approval grants");
     m.def("wf_admit", &wf_admit, "K3-WF run admission into the lowest free slots");
+    m.def("wf_admit_keep", &wf_admit_keep,
+          "K3-WF run admission with steps already done (rerun from a step)");
     m.def("wf_cancel", &wf_cancel, "K3-WF generation-checked run cancellation");
     m.def("wf_retire", &wf_retire, "K3-WF completion records + quiescent slot release");
     m.def("wf_journal", &wf_journal, "K3-WF step-transition journal pass (observer)");

@@ -516,7 +516,7 @@ def _wf_forward(name: str):
 # wf_X is reference.wf_X_ref. (Class attributes and not a __getattr__, so that
 # a subclass that watches attribute access sees them like any other method.)
 for _name in ("wf_sweep", "wf_expand", "wf_apply_dead", "wf_status", "wf_grant",
-              "wf_readmit", "wf_admit", "wf_cancel", "wf_journal", "wf_hold_scan",
+              "wf_readmit", "wf_admit", "wf_admit_keep", "wf_cancel", "wf_journal", "wf_hold_scan",
               "wf_settle", "wf_cond_eval", "wf_child_payload", "wf_apply_out",
               "wf_decide"):
     setattr(_RefOps, _name, _wf_forward(_name))

@@ -627,6 +627,82 @@ def wf_admit_ref(req_tmpl, req_cond, req_fanout,
         out_gen[i] = int(run_gen[slot])
 
 
+def wf_admit_keep_ref(req_tmpl, req_cond, req_fanout,
+                      tmpl_deps, tmpl_kind, tmpl_todo, tmpl_maxp, tmpl_delay,
+                      tmpl_nsteps,
+                      step_state, step_attempts, deps_mask, step_kind,
+                      children_todo, max_parallel, children_out, children_done,
+                      children_fail, children_emitted, next_ready, dispatch_tick,
+                      n_steps, cond_bits, run_state, run_active, run_life, run_gen,
+                      tick, free_mask, blk_scan, out_slot, out_gen, admit_count,
+                      req_keep, req_skip):
+    """wf_admit with steps already done: bit s of req_keep[i] presets step s
+    as SUCCEEDED, or SKIPPED where req_skip[i] has the bit too. A kept set
+    with a bit at or past the template's n_steps, or with a kept step that
+    depends on a step not kept, gets slot -2 and writes nothing else; that
+    is decided before the table is looked at, so -2 wins over -1. Request i
+    takes the i-th lowest FREE slot whatever became of the requests before
+    it: the slot of a refused request stays FREE."""
+    n = int(req_tmpl.shape[0])
+    if n <= 0:
+        return
+    NR = int(n_steps.shape[0])
+    TC = int(tmpl_nsteps.shape[0])
+    tick1 = int(tick[0]) + 1  # the run's first tick
+    free = torch.nonzero(run_life[:NR] == WFL_FREE).flatten().tolist()  # ascending
+    m64 = (1 << 64) - 1
+    for i in range(n):
+        tid = int(req_tmpl[i])
+        known = 0 <= tid < TC  # the host rejects the rest
+        t0 = tid if known else 0
+        ns = int(tmpl_nsteps[tid]) if known else 0
+        keep = int(req_keep[i]) & m64
+        skip = int(req_skip[i]) & keep
+        closed = keep >> ns == 0 and all(
+            int(tmpl_deps[t0 * 64 + s]) & m64 & ~keep == 0
+            for s in range(ns) if keep >> s & 1)
+        if not closed:
+            out_slot[i] = -2
+            out_gen[i] = 0
+            continue
+        if i >= len(free):
+            out_slot[i] = -1
+            out_gen[i] = 0
+            continue
+        slot = free[i]
+        fan = int(req_fanout[i])
+        row = slice(slot * 64, slot * 64 + 64)
+        trow = slice(t0 * 64, t0 * 64 + 64)
+        inside = torch.arange(64) < ns
+        kind = torch.where(inside, tmpl_kind[trow], 0)
+        todo = tmpl_todo[trow]
+        if fan > 0:
+            todo = torch.where(kind == WFK_FOR_EACH, fan, todo)
+        step_state[row] = torch.tensor(
+            [WFS_SKIPPED if skip >> s & 1 else WFS_SUCCEEDED if keep >> s & 1
+             else WFS_PENDING for s in range(64)], dtype=step_state.dtype)
+        step_attempts[row] = 0
+        deps_mask[row] = torch.where(inside, tmpl_deps[trow], 0)
+        step_kind[row] = kind
+        children_todo[row] = torch.where(inside, todo, 0)
+        max_parallel[row] = torch.where(inside, tmpl_maxp[trow], 0)
+        children_out[row] = 0
+        children_done[row] = 0
+        children_fail[row] = 0
+        children_emitted[row] = 0
+        next_ready[row] = torch.where(inside, tick1 + tmpl_delay[trow], 0)
+        dispatch_tick[row] = torch.where(inside, tick1, 0)
+        n_steps[slot] = ns
+        cond_bits[slot] = int(req_cond[i])
+        run_state[slot] = 0
+        run_active[slot] = 1
+        run_life[slot] = WFL_LIVE
+        run_gen[slot] += 1
+        out_slot[i] = slot
+        out_gen[i] = int(run_gen[slot])
+        admit_count[0] += 1
+
+
 def wf_cancel_ref(req_slot, req_gen, run_life, run_gen, run_active, run_state,
                   n_steps, step_state, cancel_count, out_ok):
     NR = int(n_steps.shape[0])

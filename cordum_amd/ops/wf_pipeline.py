@@ -521,7 +521,11 @@ class WorkflowPipeline:
         self.template_cap = TC
         self.n_templates = 0
         self._tmpl_cond: List[int] = []
-        self.tmpl_deps = torch.zeros(TC * 64, dtype=torch.int64, device=d)
+        # per template, for admit(keep=...): the CONDITION steps, and those
+        # among them without a predicate, as step masks
+        self._tmpl_cond_steps: List[int] = []
+        self._tmpl_plain_steps: List[int] = []
+        self.tmpl_deps =torch.zeros(TC * 64, dtype=torch.int64, device=d)
         self.tmpl_kind = torch.zeros(TC * 64, dtype=torch.uint8, device=d)
         self.tmpl_todo = torch.zeros(TC * 64, dtype=torch.int32, device=d)
         self.tmpl_maxp = torch.zeros(TC * 64, dtype=torch.int32, device=d)
@@ -790,15 +794,34 @@ class WorkflowPipeline:
         if self.device_conditions:
             self._add_cond_rows(t, dag, cond_recs)
         self._tmpl_cond.append(rows.cond)
+        conds = [s for s, sp in enumerate(dag.steps) if sp.kind == WFK_CONDITION]
+        self._tmpl_cond_steps.append(sum(1 << s for s in conds))
+        self._tmpl_plain_steps.append(
+            sum(1 << s for s in conds if dag.steps[s].when is None))
         self.n_templates = t + 1
         return t
 
-    def admit(self, templates: Sequence[int], cond_bits=None, fanout=None, inputs=None):
+    def admit(self, templates: Sequence[int], cond_bits=None, fanout=None, inputs=None,
+              keep=None, outs=None):
         """Admit one run per template id into the lowest FREE slots; returns
         (slots, gens). slots[i] == -1: the table was full for request i.
         `inputs[i]` (device_conditions) holds at most input_words ints in
-        int32 range, zero padded: the run's input words."""
+        int32 range, zero padded: the run's input words.
+
+        `keep[i]` starts run i with steps already done (a rerun from a step):
+        (done_mask, skipped_mask), or a bare int for (mask, 0). A step of
+        done_mask starts SUCCEEDED, one of skipped_mask (a subset) SKIPPED.
+        The done set has to lie inside the template's steps and hold every
+        dependency of each of its steps; the device checks that, and
+        slots[i] == -2 says it does not hold (such a request takes no slot;
+        the requests around it land where they would have anyway). `outs[i]`
+        (device_conditions) gives the output words of kept steps, as a
+        {step: word} dict or a 64-entry row. A kept CONDITION step's word
+        and condition bit are 1 if SUCCEEDED and 0 if SKIPPED whatever is
+        passed; a step that is not kept starts as it does without `keep`."""
         self._require_dynamic(True, "admit")
+        if keep is not None or outs is not None:
+            return self._admit_keep(templates, cond_bits, fanout, inputs, keep, outs)
         n, req = self._pack_request(templates, cond_bits, fanout, inputs)
         if n == 0:
             return [], []
@@ -833,9 +856,113 @@ class WorkflowPipeline:
         h = out.cpu()                     # the one D2H (synchronising)
         return h[:n].tolist(), h[n:].tolist()
 
-    def _pack_request(self, templates, cond_bits, fanout, inputs):
-        """Validated admit() request as (n, one host buffer): [cond as int64 |
-        template ids | fanouts | input rows]."""
+    def _admit_keep(self, templates, cond_bits, fanout, inputs, keep, outs):
+        """admit() with kept steps: one H2D of [cond | keep | skip as int64 |
+        template ids | fanouts | input rows | output rows], wf_admit_keep,
+        the side columns, one D2H."""
+        tl, cl, fl, il = self._check_request(templates, cond_bits, fanout, inputs)
+        n = len(tl)
+        if outs is not None and not self.device_conditions:
+            raise ValueError("outs need device_conditions=True")
+        kl = [0] * n if keep is None else list(keep)
+        ol = [None] * n if outs is None else list(outs)
+        if len(kl) != n or len(ol) != n:
+            raise ValueError("keep / outs must match templates in length")
+        dl = [k[0] if type(k) in (tuple, list) else k for k in kl]
+        sl = [k[1] if type(k) in (tuple, list) else 0 for k in kl]
+        for m in dl + sl:
+            if type(m) is not int or not 0 <= m < (1 << 64):
+                raise ValueError(f"keep mask {m!r} is not a 64-bit mask")
+        if any(sk & ~d for d, sk in zip(dl, sl)):
+            raise ValueError("a skipped step must be among the done steps")
+        rows = []
+        if self.device_conditions or any(self._tmpl_cond_steps):
+            for i, (d, sk) in enumerate(zip(dl, sl)):
+                # a kept CONDITION step has decided: its bit says how
+                cm = self._tmpl_cond_steps[tl[i]] & d
+                if cm:
+                    cl[i] = _i64(((cl[i] & ((1 << 64) - 1)) & ~cm) | (cm & ~sk))
+                if self.device_conditions:
+                    # a CONDITION without a predicate gets its word from its
+                    # bit, below, like one that is not kept
+                    plain = self._tmpl_plain_steps[tl[i]]
+                    rows.append(self._out_row(ol[i], d, cm, cm & ~sk & ~plain))
+        if n == 0:
+            return [], []
+        done = [d - (1 << 64) if d >> 63 else d for d in dl]
+        skipped = [s - (1 << 64) if s >> 63 else s for s in sl]
+        IW = self.input_words if self.device_conditions else 0
+        OW = 64 if self.device_conditions else 0
+        req = torch.empty(8 * n + n * IW + n * OW, dtype=torch.int32)
+        req[:6 * n].view(torch.int64).copy_(
+            torch.tensor(cl + done + skipped, dtype=torch.int64))
+        req[6 * n:8 * n] = torch.tensor(tl + fl, dtype=torch.int32)
+        if IW:
+            req[8 * n:8 * n + n * IW] = torch.tensor(il, dtype=torch.int32)
+            req[8 * n + n * IW:] = torch.tensor(rows, dtype=torch.int32).flatten()
+        req = req.to(self.device)         # the one H2D
+        m64 = req[:6 * n].view(torch.int64)
+        cond, kept, skip = m64[:n], m64[n:2 * n], m64[2 * n:]
+        tmpl, fan = req[6 * n:7 * n], req[7 * n:8 * n]
+        out = torch.empty(2 * n, dtype=torch.int32, device=self.device)
+        slots = out[:n]
+        self.ext.wf_admit_keep(
+            tmpl, cond, fan,
+            self.tmpl_deps, self.tmpl_kind, self.tmpl_todo, self.tmpl_maxp,
+            self.tmpl_delay, self.tmpl_nsteps,
+            self.step_state, self.step_attempts, self.deps_mask, self.step_kind,
+            self.children_todo, self.max_parallel, self.children_out,
+            self.children_done, self.children_fail, self.children_emitted,
+            self.next_ready, self.dispatch_tick, self.n_steps, self.cond_bits,
+            self.run_state, self.run_active, self.run_life, self.run_gen,
+            self.tick_buf, self._free_mask, self._blk_scan,
+            slots, out[n:], self.admit_count, kept, skip)
+        if self.step_policy or self.device_conditions:
+            # every refused request, -1 or -2, goes to the spare row: -2 mod
+            # (NR + 1) would be the table's last run
+            dst = torch.where(slots < 0, self.NR, slots).long()
+            self._run_tmpl_buf[dst] = tmpl
+            if self.device_conditions:
+                self._run_input_buf.view(-1, IW)[dst] = req[8 * n:8 * n + n * IW].view(-1, IW)
+                # the kept steps' words; elsewhere what _admit_cond_rows writes
+                plain = self._tmpl_plain_cond.view(-1, 64)[tmpl.long()]
+                bits = ((cond[:, None] >> self._bit_idx[None, :]) & 1).to(torch.int32)
+                self._step_out_buf.view(-1, 64)[dst] = \
+                    req[8 * n + n * IW:].view(-1, 64) + bits * plain
+        if self.external and self._any_ttl:
+            self._admit_hold_ttl(slots, tmpl)
+        h = out.cpu()                     # the one D2H (synchronising)
+        return h[:n].tolist(), h[n:].tolist()
+
+    def _out_row(self, words, done: int, decided: int, true: int) -> List[int]:
+        """The 64 output words a request passes for its kept steps. The steps
+        of `decided` are kept CONDITION steps: theirs is the bit of `true`."""
+        row = [0] * 64
+        if words is None:
+            items = ()
+        elif isinstance(words, dict):
+            items = words.items()
+        elif len(words) == 64:
+            items = enumerate(words)
+        else:
+            raise ValueError("an outs row has 64 entries")
+        for s, v in items:
+            if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < 64:
+                raise ValueError(f"outs names step {s!r}")
+            if isinstance(v, bool) or not isinstance(v, int) \
+                    or not _I32_MIN <= v <= _I32_MAX:
+                raise ValueError(f"output word {v!r} is not an int32")
+            if not done >> s & 1 and (v or isinstance(words, dict)):
+                raise ValueError(f"outs gives a word for step {s}, which is not kept")
+            row[s] = v
+        for s in range(64 if decided else 0):
+            if decided >> s & 1:
+                row[s] = true >> s & 1
+        return row
+
+    def _check_request(self, templates, cond_bits, fanout, inputs):
+        """Validated admit() request as lists: template ids, signed condition
+        bits, fanouts and the flat, zero-padded input rows."""
         tl = [int(t) for t in templates]
         n = len(tl)
         for t in tl:
@@ -868,6 +995,14 @@ class WorkflowPipeline:
                             or not _I32_MIN <= v <= _I32_MAX:
                         raise ValueError(f"input word {v!r} is not an int32")
                 il += list(r) + [0] * (IW - len(r))
+        return tl, cl, fl, il
+
+    def _pack_request(self, templates, cond_bits, fanout, inputs):
+        """Validated admit() request as (n, one host buffer): [cond as int64 |
+        template ids | fanouts | input rows]."""
+        tl, cl, fl, il = self._check_request(templates, cond_bits, fanout, inputs)
+        n = len(tl)
+        IW = self.input_words if self.device_conditions else 0
         if n == 0:
             return 0, None
         req = torch.empty(4 * n + n * IW, dtype=torch.int32)

@@ -32,6 +32,12 @@ whose guard is false shows as PENDING -> SKIPPED in the events, which
 status succeeded; the host engine completes such a step as succeeded without
 recording an event. That is the one difference.
 
+`rerun_from()` starts a new run of a run's workflow with the same input and
+with the transitive dependencies of a chosen step already finished, as the
+host engine's `rerun_from` does: the source is a run in the table, a queued
+one, or one of the `retain` last completed ones, whose final step states and
+output words the table then keeps.
+
 Wiring an API route to this table, and materialising job results (a step's
 output word is a checksum, not the job's result document), are not done here.
 """
@@ -39,7 +45,7 @@ from __future__ import annotations
 
 import math
 import re
-from collections import deque
+from collections import OrderedDict, deque
 from typing import Any, Deque, Dict, List, NamedTuple, Optional, Tuple, Union
 
 from ..ops.reference import wf_backoff_ref
@@ -388,9 +394,15 @@ def dag_from_workflow(workflow: Any, items_len: int,
 class DeviceRunTable:
     """Run ids over a dynamic-mode `WorkflowPipeline`."""
 
-    def __init__(self, pipe: WorkflowPipeline, store=None, clock=SYSTEM_CLOCK):
+    def __init__(self, pipe: WorkflowPipeline, store=None, clock=SYSTEM_CLOCK,
+                 retain: int = 0):
+        """`retain` > 0 keeps the final step states (and, on a pipeline with
+        device_conditions, the output words) of that many most recently
+        completed runs, so that rerun_from() can start from them."""
         if not getattr(pipe, "dynamic", False):
             raise RuntimeError("DeviceRunTable needs a dynamic-mode pipeline")
+        if int(retain) < 0:
+            raise ValueError("retain is a count of runs")
         self.pipe = pipe
         self.store = store                # a WorkflowStore, or None
         self._clock = clock
@@ -403,8 +415,22 @@ class DeviceRunTable:
         self._handle: Dict[str, Tuple[int, int]] = {}
         self._run_of: Dict[Tuple[int, int], str] = {}
         self._tmpl_inputs: Dict[int, List[str]] = {}  # template id -> input field names
-        # (run id, template, cond bits, fanout, input words)
-        self._queue: Deque[Tuple[str, int, int, int, Tuple[int, ...]]] = deque()
+        # run id -> (template, cond bits, fanout, input words): what a rerun
+        # submits again
+        self._req_of: Dict[str, Tuple[int, int, int, Tuple[int, ...]]] = {}
+        # run id -> the steps it was admitted with as done, whose one
+        # journal event each is still to come (and to be dropped)
+        self._kept_of: Dict[str, int] = {}
+        self._retain = int(retain)
+        # run id -> (request, final step states, output words or None) of
+        # the last `retain` completed runs, oldest first
+        self._retained: "OrderedDict[str, Tuple[tuple, List[int], Optional[List[int]]]]" = \
+            OrderedDict()
+        self._tmpl_depmask: Dict[int, List[int]] = {}  # template id -> deps per step
+        # (run id, template, cond bits, fanout, input words, (done, skipped)
+        # step masks, {step: output word} of the done steps or None)
+        self._queue: Deque[Tuple[str, int, int, int, Tuple[int, ...],
+                                 Tuple[int, int], Optional[Dict[int, int]]]] = deque()
         self._queued_ids: set = set()     # run ids in _queue
         self._reported: List[Tuple[str, str]] = []  # queued runs cancelled
 
@@ -424,18 +450,29 @@ class DeviceRunTable:
         """Admit the requests in order; returns how many got a slot (the
         device accepts a prefix)."""
         extra = {}
-        if getattr(self.pipe, "device_conditions", False):
+        conditions = getattr(self.pipe, "device_conditions", False)
+        if conditions:
             extra["inputs"] = [r[4] for r in reqs]
+        if any(r[5][0] for r in reqs):      # a rerun among them
+            extra["keep"] = [r[5] for r in reqs]
+            if conditions:
+                extra["outs"] = [r[6] for r in reqs]
         slots, gens = self.pipe.admit([r[1] for r in reqs],
                                       cond_bits=[r[2] for r in reqs],
                                       fanout=[r[3] for r in reqs], **extra)
         n = 0
         for r, slot, gen in zip(reqs, slots, gens):
+            if slot == -2:
+                # rerun_from() keeps a closed set of the template's steps
+                raise RuntimeError(f"the device refused the kept steps of run {r[0]!r}")
             if slot < 0:
                 break
             self._handle[r[0]] = (slot, gen)
             self._run_of[(slot, gen)] = r[0]
             self._tmpl_of[r[0]] = r[1]
+            self._req_of[r[0]] = r[1:5]
+            if r[5][0]:
+                self._kept_of[r[0]] = r[5][0]
             n += 1
         return n
 
@@ -499,14 +536,104 @@ class DeviceRunTable:
             raise ValueError(f"unregistered template id {template_id}")
         if not 0 <= int(fanout) <= self.pipe.CB:
             raise ValueError(f"fanout {fanout} can never be emitted")
-        req = (run_id, int(template_id), int(cond_bits), int(fanout),
-               self._input_words(int(template_id), input))
+        return self._submit((run_id, int(template_id), int(cond_bits), int(fanout),
+                             self._input_words(int(template_id), input), (0, 0), None))
+
+    def _submit(self, req) -> bool:
         # nobody overtakes a waiting submission
         if not self._queue and self._admit([req]) == 1:
             return True
         self._queue.append(req)
-        self._queued_ids.add(run_id)
+        self._queued_ids.add(req[0])
         return False
+
+    def _deps_of(self, template_id: int) -> List[int]:
+        """The dependency mask of every step of a template, as the device
+        holds it."""
+        deps = self._tmpl_depmask.get(template_id)
+        if deps is None:
+            row = self.pipe.tmpl_deps[template_id * 64:template_id * 64 + 64]
+            deps = self._tmpl_depmask[template_id] = \
+                [d & ((1 << 64) - 1) for d in row.cpu().tolist()]
+        return deps
+
+    def _source(self, run_id: str):
+        """(request, step states, output words or None) of the run a rerun
+        starts from: a resident run as the device holds it now, then a
+        retained record, then a queued run, which has finished nothing."""
+        conditions = getattr(self.pipe, "device_conditions", False)
+        h = self._handle.get(run_id)
+        if h is not None:
+            row = slice(h[0] * 64, h[0] * 64 + 64)
+            return (self._req_of[run_id], self.pipe.step_state[row].cpu().tolist(),
+                    self.pipe.step_out[row].cpu().tolist() if conditions else None)
+        if run_id in self._retained:
+            return self._retained[run_id]
+        for q in self._queue:
+            if q[0] == run_id:
+                return q[1:5], [WFS_PENDING] * 64, [0] * 64 if conditions else None
+        raise KeyError(run_id)
+
+    def rerun_from(self, run_id: str, step: Union[str, int] = "",
+                   new_run_id: Optional[str] = None) -> str:
+        """Start a new run of `run_id`'s workflow with the same input, as the
+        host engine's rerun_from does; returns its id (`new_run_id`, or a
+        fresh one). With `step` (a step id or index) every transitive
+        dependency of that step, never the step itself, starts as finished,
+        in the state and with the output word it has in the source run; with
+        step "" nothing is kept. The source is a run in the table, one of the
+        `retain` last completed ones, or a queued one (KeyError otherwise).
+        ValueError "run id required", "step not found" and "dependency X not
+        succeeded" as the host engine raises them; a dependency counts as
+        succeeded if it is SUCCEEDED or SKIPPED (a false condition) on the
+        device. If the table is full the rerun waits in the submissions'
+        FIFO. With a store that holds the source run, the new run's record
+        is created with the host engine's rerun fields."""
+        from ..utils.ids import new_id
+
+        if not run_id:
+            raise ValueError("run id required")
+        req, states, outs = self._source(run_id)
+        tmpl = req[0]
+        done = skipped = 0
+        if step != "":
+            s = self._step_index(tmpl, step)
+            deps = self._deps_of(tmpl)
+            todo = deps[s]
+            while todo:                 # the transitive dependencies of s
+                d = todo.bit_length() - 1
+                todo &= ~(1 << d)
+                if not done >> d & 1:
+                    done |= 1 << d
+                    todo |= deps[d] & ~done
+        ids = self._info(tmpl)[1]
+        for d in range(64):
+            if done >> d & 1:
+                if states[d] == WFS_SKIPPED:
+                    skipped |= 1 << d
+                elif states[d] != WFS_SUCCEEDED:
+                    raise ValueError(
+                        f"dependency {ids[d] if ids else d} not succeeded")
+        new = new_id() if new_run_id is None else new_run_id
+        if self._known(new):
+            raise ValueError(f"run {new!r} is already live or queued")
+        words = None if outs is None else {d: outs[d] for d in range(64) if done >> d & 1}
+        if self.store is not None:
+            self._store_rerun(run_id, step, new, ids, done)
+        self._submit((new,) + tuple(req) + ((done, skipped), words))
+        return new
+
+    def _store_rerun(self, run_id: str, step: Union[str, int], new: str,
+                     ids: Optional[List[str]], done: int) -> None:
+        from .engine import rerun_record
+
+        run = self._stored_run(run_id)
+        if run is None:
+            return
+        step_id = step if isinstance(step, str) else (ids[step] if ids else "")
+        deps = {ids[d] for d in range(64) if done >> d & 1} if ids else set()
+        self.store.create_run(rerun_record(run, step_id, deps, new, self._clock.now(),
+                                           require_succeeded=False))
 
     def cancel(self, run_id: str) -> bool:
         """Cancel a run. A still-queued submission is dropped without
@@ -590,6 +717,12 @@ class DeviceRunTable:
         for slot, gen, step, f, t, stamp in zip(slots, gens, steps, frm, to, stamps):
             run_id = self._run_of.get((slot, gen))
             if run_id is None:
+                continue
+            kept = self._kept_of.get(run_id, 0)
+            if kept >> step & 1 and f == WFS_PENDING and t in (WFS_SUCCEEDED, WFS_SKIPPED):
+                # a step the rerun was admitted with as done: the journal sees
+                # it once, as finishing in the run's first pass. Nothing ran.
+                self._kept_of[run_id] = kept & ~(1 << step)
                 continue
             wf_id, ids, kinds = self._info(self._tmpl_of[run_id])
             step_id = ids[step] if ids is not None and step < len(ids) else ""
@@ -680,20 +813,44 @@ class DeviceRunTable:
             # handle, and its slot cannot be released with changes unseen
             self._drain_events()
         slots, gens, states = self.pipe.drain_completed()
+        ended: List[Tuple[int, str, tuple]] = []
         for slot, gen, state in zip(slots, gens, states):
             run_id = self._run_of.pop((slot, gen), None)
             if run_id is None:
                 continue
             del self._handle[run_id]
             tmpl = self._tmpl_of.pop(run_id)
+            ended.append((slot, run_id, self._req_of.pop(run_id)))
+            self._kept_of.pop(run_id, None)
             out.append((run_id, _STATUS[state]))
             if self.store is not None:
                 self._store_completion(run_id, _STATUS[state], self._info(tmpl)[0])
+        if self._retain and ended:
+            # before the admissions below: a reported row, DRAINING or freed
+            # just now, keeps its content until the next admission takes it
+            self._retain_rows(ended)
         if self._queue:
             reqs = list(self._queue)
             for _ in range(self._admit(reqs)):
                 self._queued_ids.discard(self._queue.popleft()[0])
         return out
+
+    def _retain_rows(self, ended) -> None:
+        """Remember the rows of the runs that just ended: one indexed load of
+        their step states (and output words) and one D2H."""
+        import torch
+
+        idx = torch.tensor([e[0] for e in ended], dtype=torch.int64).to(self.pipe.device)
+        rows = self.pipe.step_state.view(-1, 64)[idx]
+        conditions = getattr(self.pipe, "device_conditions", False)
+        if conditions:
+            rows = torch.cat([rows.to(torch.int32), self.pipe.step_out.view(-1, 64)[idx]], 1)
+        rows = rows.cpu().tolist()
+        for (_, run_id, req), row in zip(ended, rows):
+            self._retained[run_id] = (req, row[:64], row[64:] if conditions else None)
+            self._retained.move_to_end(run_id)
+        while len(self._retained) > self._retain:
+            self._retained.popitem(last=False)
 
     def tick(self) -> None:
         self.pipe.tick()

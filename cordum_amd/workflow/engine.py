@@ -119,34 +119,7 @@ class Engine:
                     raise ValueError("step not found")
                 _collect_dependencies(wf, step_id, deps)
             now = self.clock.now()
-            new_run = WorkflowRun(
-                id=new_id(),
-                workflow_id=run.workflow_id,
-                org_id=run.org_id,
-                team_id=run.team_id,
-                input=json.loads(json.dumps(run.input)),
-                context=_clone_context_for_deps(run.context, deps),
-                status=RUN_PENDING,
-                triggered_by=run.triggered_by,
-                created_at=now,
-                updated_at=now,
-                rerun_of=run.id,
-                rerun_step=step_id,
-                dry_run=dry_run,
-                labels=dict(run.labels),
-                metadata=dict(run.metadata),
-            )
-            new_run.metadata["rerun_of"] = run.id
-            if step_id:
-                new_run.metadata["rerun_step"] = step_id
-            if dry_run:
-                new_run.metadata["dry_run"] = "true"
-                new_run.labels["dry_run"] = "true"
-            for dep in deps:
-                prev = run.steps.get(dep)
-                if prev is None or prev.status != STEP_SUCCEEDED:
-                    raise ValueError(f"dependency {dep} not succeeded")
-                new_run.steps[dep] = prev.clone()
+            new_run = rerun_record(run, step_id, deps, new_id(), now, dry_run=dry_run)
             self.store.create_run(new_run)
             return new_run.id
 
@@ -1034,6 +1007,48 @@ def _clone_context_for_deps(ctx: Dict[str, Any], deps: set) -> Dict[str, Any]:
         if kept:
             out["steps"] = json.loads(json.dumps(kept))
     return out
+
+
+def rerun_record(run: WorkflowRun, step_id: str, deps: set, new_run_id: str,
+                 now: float, dry_run: bool = False,
+                 require_succeeded: bool = True) -> WorkflowRun:
+    """The record of a rerun of `run` from `step_id` (RerunFrom): the same
+    input, the context and the StepRuns of the dependencies `deps` cloned.
+    Raises ValueError for a dependency the record does not show succeeded,
+    unless the caller has established that itself (`require_succeeded`
+    False: the device run table decides by the device's step states, and a
+    dependency the record lacks is cloned as succeeded)."""
+    new_run = WorkflowRun(
+        id=new_run_id,
+        workflow_id=run.workflow_id,
+        org_id=run.org_id,
+        team_id=run.team_id,
+        input=json.loads(json.dumps(run.input)),
+        context=_clone_context_for_deps(run.context, deps),
+        status=RUN_PENDING,
+        triggered_by=run.triggered_by,
+        created_at=now,
+        updated_at=now,
+        rerun_of=run.id,
+        rerun_step=step_id,
+        dry_run=dry_run,
+        labels=dict(run.labels),
+        metadata=dict(run.metadata),
+    )
+    new_run.metadata["rerun_of"] = run.id
+    if step_id:
+        new_run.metadata["rerun_step"] = step_id
+    if dry_run:
+        new_run.metadata["dry_run"] = "true"
+        new_run.labels["dry_run"] = "true"
+    for dep in deps:
+        prev = run.steps.get(dep)
+        if require_succeeded and (prev is None or prev.status != STEP_SUCCEEDED):
+            raise ValueError(f"dependency {dep} not succeeded")
+        new_run.steps[dep] = prev.clone() if prev is not None \
+            else StepRun(step_id=dep, status=STEP_SUCCEEDED)
+        new_run.steps[dep].status = STEP_SUCCEEDED
+    return new_run
 
 
 def _collect_cancelable_jobs(sr: StepRun) -> List[str]:

@@ -59,11 +59,27 @@ runs/s of both, the ratio, and the predicate counters. --cond-pass ROWS runs
 nothing but the quiet passes of wf_cond_eval (nothing PENDING) and wf_settle
 (nothing DISPATCHED) alone, alternating, at that size.
 
+With --rerun nothing but this runs: `admit(keep=...)` (wf_admit_keep, every
+request keeping the three steps before `final`) against plain `admit()`, per
+call by device events, with n = 1, 256 and 4096 requests on a table of --runs
+slots that is half full. The two calls alternate, 8 pairs per n after a
+warm-up pair, and so does their order within a pair; what a call admitted is
+cancelled and drained before the next one, so every call sees the same table.
+The time of a call is the host's packing of the request, the H2D copy, the
+launches and the D2H copy that ends it; the three launches of the two
+bindings are timed alone as well, on requests that are on the device already
+(`wf_admit_keep_launches_us`, `wf_admit_launches_us`). With --other-ext PATH (a build of the
+extension from another commit) plain `admit()` on this build is timed against
+plain `admit()` on that one in the same way, on one pipeline whose tables
+both use. For illustration it also counts the child jobs emitted and the
+ticks to completion of one full run and of a rerun of it from `final`.
+
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --events
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --approvals
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --step-policy
     python tools/wf_churn_bench.py --runs 2048 --fanout 256 --repeats 5 --conditions
+    python tools/wf_churn_bench.py --runs 8192 --fanout 256 --rerun
 """
 import argparse
 import json
@@ -110,6 +126,11 @@ def main() -> int:
                          "against the predicate evaluated before admission")
     ap.add_argument("--cond-pass", type=int, default=0, metavar="ROWS",
                     help="only time the quiet wf_cond_eval and wf_settle passes at ROWS rows")
+    ap.add_argument("--rerun", action="store_true",
+                    help="only time admit(keep=...) against admit(), per call")
+    ap.add_argument("--other-ext", metavar="PATH", default=None,
+                    help="with --rerun: a second build of the extension (.so) to time "
+                         "plain admit() against")
     ap.add_argument("--allow-cpu", action="store_true",
                     help="rehearse the host logic on the reference backend (no timings)")
     args = ap.parse_args()
@@ -272,6 +293,117 @@ def main() -> int:
         print(json.dumps({"metric": "quiet wf_cond_eval pass vs quiet wf_settle pass, alone",
                           "unit": "us", "timed": bool(use_gpu),
                           "pass_times": [cond_pass_times(ext, args.cond_pass)]}))
+        return 0
+
+    if args.rerun:
+        pipe = WorkflowPipeline(dags=[dag], dynamic_capacity=args.runs, **common)
+        this_ext, other_ext = pipe.ext, None
+        if args.other_ext:
+            import importlib.util
+
+            spec = importlib.util.spec_from_file_location("cordum_hip_ops", args.other_ext)
+            other_ext = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(other_ext)
+        held, _ = pipe.admit([0] * (args.runs // 2))
+        assert min(held) >= 0
+        KEEP = 0b0111                              # seed, fan-out and approval done
+
+        def release(got):
+            """Cancel and drain what a timed call admitted: the same table again."""
+            if torch.is_tensor(got):               # a binding's [slots | gens]
+                h = got.cpu().tolist()
+                got = h[:len(h) // 2], h[len(h) // 2:]
+            slots, gens = got
+            live = [(s, g) for s, g in zip(slots, gens) if s >= 0]
+            assert all(pipe.cancel([s for s, _ in live], [g for _, g in live]))
+            done, _, _ = pipe.drain_completed()
+            assert sorted(done) == sorted(s for s, _ in live)
+            return len(live)
+
+        def plain_on(ext):
+            def call(n):
+                pipe.ext = ext
+                try:
+                    return pipe.admit([0] * n)
+                finally:
+                    pipe.ext = this_ext
+            return call
+
+        def binding(name):
+            """The three launches alone, on a request that is on the device."""
+            def call(n):
+                req = torch.zeros(4 * n, dtype=torch.int32, device=device)
+                masks = torch.full((2 * n,), KEEP, dtype=torch.int64, device=device)
+                masks[n:] = 0
+                out = torch.empty(2 * n, dtype=torch.int32, device=device)
+                tail = (masks[:n], masks[n:]) if name == "wf_admit_keep" else ()
+                sync()
+                return lambda _n: launch(name, req, out, n, tail)
+            return call
+
+        def launch(name, req, out, n, tail):
+            getattr(this_ext, name)(
+                req[2 * n:3 * n], req[:2 * n].view(torch.int64), req[3 * n:],
+                pipe.tmpl_deps, pipe.tmpl_kind, pipe.tmpl_todo, pipe.tmpl_maxp,
+                pipe.tmpl_delay, pipe.tmpl_nsteps,
+                pipe.step_state, pipe.step_attempts, pipe.deps_mask, pipe.step_kind,
+                pipe.children_todo, pipe.max_parallel, pipe.children_out,
+                pipe.children_done, pipe.children_fail, pipe.children_emitted,
+                pipe.next_ready, pipe.dispatch_tick, pipe.n_steps, pipe.cond_bits,
+                pipe.run_state, pipe.run_active, pipe.run_life, pipe.run_gen,
+                pipe.tick_buf, pipe._free_mask, pipe._blk_scan,
+                out[:n], out[n:], pipe.admit_count, *tail)
+            return out
+
+        def alternate(a, b, n, pairs=8):
+            ta, tb = Timer(), Timer()
+            admitted = set()
+            for i in range(pairs + 1):
+                # the order within a pair alternates too: whichever call
+                # comes first in a pair starts on an idle device
+                for timer, fn in ((ta, a), (tb, b))[::1 if i % 2 else -1]:
+                    admitted.add(release(timer(fn, n)))
+                sync()
+                if i == 0:                         # warm-up pair
+                    ta.take_ms(), tb.take_ms()
+            assert len(admitted) == 1              # every call found the same room
+            if not use_gpu:
+                return admitted.pop(), None, None
+            return (admitted.pop(), spread([1000 * x for x in ta.take_ms()]),
+                    spread([1000 * x for x in tb.take_ms()]))
+
+        rows = []
+        for n in (1, 256, 4096):
+            k, keep_us, plain_us = alternate(
+                lambda m: pipe.admit([0] * m, keep=[KEEP] * m), plain_on(this_ext), n)
+            row = {"n": n, "admitted": k, "admit_keep_us": keep_us, "admit_us": plain_us}
+            _, keep_us, plain_us = alternate(
+                binding("wf_admit_keep")(n), binding("wf_admit")(n), n)
+            row.update(wf_admit_keep_launches_us=keep_us, wf_admit_launches_us=plain_us)
+            if other_ext is not None:
+                _, here_us, there_us = alternate(plain_on(this_ext), plain_on(other_ext), n)
+                row.update(admit_this_build_us=here_us, admit_other_build_us=there_us)
+            rows.append(row)
+
+        def to_the_end(keep):
+            (slot,), _ = pipe.admit([0], keep=None if keep is None else [keep])
+            for t in range(1, 200):
+                pipe.tick()
+                done, _, states = pipe.drain_completed()
+                if slot in done:
+                    assert states[done.index(slot)] == WFS_SUCCEEDED
+                    return {"ticks": t,
+                            "children": int(pipe.children_emitted[slot * 64:slot * 64 + 64].sum())}
+            raise AssertionError("the run did not end")
+
+        release(([s for s in held], [1] * len(held)))
+        print(json.dumps({
+            "metric": "admit(keep=...) vs admit() per call, alternating, device events "
+                      "(config #3: 1->%d fan-out + approval; table half full)" % args.fanout,
+            "unit": "us", "timed": bool(use_gpu), "runs": args.runs, "pairs": 8,
+            "calls": rows,
+            "full_run": to_the_end(None), "rerun_from_final": to_the_end(KEEP),
+        }))
         return 0
 
     if args.conditions:
